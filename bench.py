@@ -8,10 +8,13 @@ pairs: image pyramid -> model forward -> reconstruct -> 4-scale loss ->
 backward -> Adam.  N>1: one process per GPU (torchrun), DDP over RCCL with
 SyncBatchNorm semantics (reference parallel_main.py:156-158), weak scaling.
 
-Prints ONE JSON line (rank 0) with a ``roofline`` object for the dominant
-kernel (measured with HIP events around its launches on the launch stream)
-and a ``cpu_baseline`` (the oracle's CPU train step on a bounded sample,
-rank 0, N=1 only).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times
+``--steps`` steps, writes the last step's outputs when ``--dump-outputs DIR``
+is given, and prints the line (``value``, ``ms_per_step``).  ``--full`` also
+runs the N=1 legs reported beside the value: a ``roofline`` object for the
+dominant kernel (measured with HIP events around its launches on the launch
+stream), a ``cpu_baseline`` (the oracle's CPU train step on a bounded
+sample), the loader-fed, eager and fp32 lines and the loss delta.
 """
 from __future__ import annotations
 
@@ -46,6 +49,13 @@ def parse():
     ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp32'])
     ap.add_argument('--loss-type', default='bayesian', choices=['l1', 'bayesian', 'log_bayesian'])
     ap.add_argument('--config', default='config.yml')
+    ap.add_argument('--full', action='store_true',
+                    help='N=1: after the timed steps also run the legs reported beside the '
+                         'value (loader, eager, roofline, fp32, CPU baseline, loss delta); '
+                         'the options below select among them')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (losses, updated parameters '
+                         'and BN buffers) as DIR/<name>.npy (float32)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--loader-steps', type=int, default=20,
@@ -652,6 +662,37 @@ def time_fp32(cfg, device, left, right, scale, batch, warmup, steps):
             'dtype': 'fp32'}
 
 
+# --------------------------------------------------------- dump outputs ----
+DUMP_SAMPLE = 4_000_000  # elements kept of a larger array (16 MB as float32)
+
+
+def dump_outputs(path, dl, el, m):
+    """What a caller of the timed step holds after its last step, as
+    ``path/<name>.npy`` (float32): the two returned losses, and the state the
+    step updated -- every parameter (``params``) and every BN buffer
+    (``buffers``), each flattened in ``named_parameters`` / ``named_buffers``
+    order and concatenated.  An array above DUMP_SAMPLE elements is reduced
+    to a fixed sample of that many (sorted indices of a seeded permutation),
+    the same from run to run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+
+    def flat(tensors):
+        ts = [t.detach().reshape(-1).float() for t in tensors]
+        v = torch.cat(ts) if ts else torch.zeros(0)
+        if v.numel() > DUMP_SAMPLE:
+            g = torch.Generator(device='cpu').manual_seed(0)
+            idx = torch.randperm(v.numel(), generator=g)[:DUMP_SAMPLE].sort().values
+            v = v[idx.to(v.device)]
+        return v.cpu().numpy().astype(np.float32)
+    arrays = {'disp_loss': dl.detach().float().reshape(1).cpu().numpy(),
+              'error_loss': el.detach().float().reshape(1).cpu().numpy(),
+              'params': flat(p for _, p in m.named_parameters()),
+              'buffers': flat(b for _, b in m.named_buffers())}
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), arr)
+
+
 def main():
     a = parse()
     if a.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -746,6 +787,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
     losses = (float(dl.detach()), float(el.detach()))
+    if a.dump_outputs and rank == 0:  # before any leg steps the model further
+        dump_outputs(a.dump_outputs, dl, el, m)
     total = a.batch * world * a.steps
     out = {
         'metric': 'stereo-pairs/sec (train step) at 256x512, 1/2/4/8 MI355X; loss delta vs ref',
@@ -777,12 +820,15 @@ def main():
             print(json.dumps(out), file=json_out, flush=True)
         dist.destroy_process_group()
         return
-    errors = {}
-    legs = post_timing_legs(a, run, use_graph, m, lf, opt, left, right, scale, cfg, device,
-                            cap_stream, errors)
-    out.update(legs)
-    if errors:
-        out['leg_errors'] = errors
+    if a.full:
+        errors = {}
+        legs = post_timing_legs(a, run, use_graph, m, lf, opt, left, right, scale, cfg, device,
+                                cap_stream, errors)
+        out.update(legs)
+        if errors:
+            out['leg_errors'] = errors
+    else:
+        out['legs'] = 'plain run: measured value only (--full runs the legs beside it)'
     print(json.dumps(out), file=json_out, flush=True)
     if dp:
         dist.destroy_process_group()

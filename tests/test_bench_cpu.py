@@ -57,6 +57,48 @@ def test_bench_parses_gpus_flag():
     assert os.path.exists(os.path.join(REPO, 'tests', 'golden', 'traj_c2.npz'))
 
 
+def test_plain_run_is_the_default():
+    """``--full`` (the legs beside the value) and ``--dump-outputs`` are off
+    unless asked for."""
+    import bench
+    old = sys.argv
+    try:
+        sys.argv = ['bench.py', '--gpus', '1', '--steps', '7', '--warmup', '2']
+        a = bench.parse()
+        sys.argv = ['bench.py', '--full', '--dump-outputs', 'somewhere']
+        b = bench.parse()
+    finally:
+        sys.argv = old
+    assert not a.full and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    assert b.full and b.dump_outputs == 'somewhere'
+
+
+def test_dump_outputs_writes_float32_arrays(tmp_path, monkeypatch):
+    """dump_outputs: the losses, every parameter and every buffer as float32
+    .npy files; an array above the cap becomes the same seeded sample on
+    every call."""
+    import numpy as np
+    import torch
+    import bench
+    torch.manual_seed(3)
+    m = torch.nn.Sequential(torch.nn.Conv2d(3, 5, 3), torch.nn.BatchNorm2d(5))
+    dl, el = torch.tensor(0.25), torch.tensor(1.5, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / 'a'), dl, el, m)
+    got = {f[:-4]: np.load(tmp_path / 'a' / f) for f in sorted(os.listdir(tmp_path / 'a'))}
+    assert sorted(got) == ['buffers', 'disp_loss', 'error_loss', 'params']
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert got['disp_loss'].tolist() == [0.25] and got['error_loss'].tolist() == [1.5]
+    want = torch.cat([p.detach().reshape(-1) for p in m.parameters()]).numpy()
+    assert np.array_equal(got['params'], want)
+    assert got['buffers'].size == 5 + 5 + 1  # running mean / var, batches tracked
+    monkeypatch.setattr(bench, 'DUMP_SAMPLE', 40)
+    bench.dump_outputs(str(tmp_path / 'b'), dl, el, m)
+    bench.dump_outputs(str(tmp_path / 'c'), dl, el, m)
+    s1, s2 = np.load(tmp_path / 'b' / 'params.npy'), np.load(tmp_path / 'c' / 'params.npy')
+    assert s1.size == 40 and np.array_equal(s1, s2)
+    assert np.isin(s1, want).all()
+
+
 def test_post_timing_leg_failure_keeps_the_line(monkeypatch):
     """A leg after the timed region that raises (here the CPU baseline and
     the eager comparison) is recorded in ``leg_errors``; the other legs and

@@ -82,11 +82,12 @@ def test_nodes10_schema():
     assert sum(p.numel() for p in m.parameters()) == 35_442_189
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference/graphs'), reason='reference absent')
 def test_gpickle_reader_matches_json():
+    """the reference's own nodes_5_seed_42 stage graphs (its networkx pickles,
+    stored as fixtures) through the opcode reader against our JSON files"""
     from model.graph import load_graph
     for s in range(1, 6):
-        a = load_graph(f'/root/reference/graphs/nodes_5_seed_42/stage_{s}.gpickle')
+        a = load_graph(os.path.join(REPO, f'tests/golden/graphs_nodes_5_seed_42/stage_{s}.gpickle'))
         b = load_graph(os.path.join(REPO, f'graphs/nodes_5_seed_42/stage_{s}.json'))
         assert a == b
 

@@ -15,10 +15,11 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 280 --timeout
 tail -3 $OUT/gpu_tests.log
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { echo SMOKE FAILED; tail -20 $OUT/smoke.log; exit 1; }
 tail -1 $OUT/smoke.log
-timeout -k 10 600 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err || { echo BENCH FAILED; tail -30 $OUT/bench.err; exit 1; }
+timeout -k 10 600 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { echo BENCH FAILED; tail -30 $OUT/bench.err; exit 1; }
 cut -c1-200 $OUT/bench.json
+ROOT=$PWD
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$OUT/bprof -o run -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline > $GRAFT_REPO_ROOT/$OUT/bench_prof.json 2> $GRAFT_REPO_ROOT/$OUT/bench_prof.err || { echo BENCH PROF FAILED; exit 1; }
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$OUT/bprof -o run -- python3 $ROOT/bench.py --full --no-cpu-baseline > $ROOT/$OUT/bench_prof.json 2> $ROOT/$OUT/bench_prof.err || { echo BENCH PROF FAILED; exit 1; }
 cd $GRAFT_REPO_ROOT
 cp $(find $OUT/bprof -name '*kernel_stats.csv' | head -1) $OUT/bench_kernel_stats.csv
 rm -f $(find $OUT/bprof -name '*kernel_trace.csv')
