@@ -495,6 +495,28 @@ int um_l1_mean(int dtype, const void* a, const void* b, long n, double* ws, floa
                hipStream_t stream);
 int um_l1_mean_bwd(int dtype, const void* a, const void* b, long n, const float* g, void* da,
                    void* db, hipStream_t stream);
+/* nn.MSELoss / nn.BCELoss (reduction 'mean') of N probabilities p against
+ * step labels y[n] = 1 for n < n_real, else 0, which are never materialised:
+ * replaces ones_like + the ATen loss in GeneratorLoss (reference
+ * train/loss.py:331-337, n_real = N) and zeros_like + the slice fill + the
+ * ATen loss in run_discriminator (train/utils.py:266-273, n_real =
+ * batch_size).  MSE: mean (p-y)^2; BCE: -mean(y max(log p, -100) + (1-y)
+ * max(log1p(-p), -100)), finite at a saturated p of exactly 0 or 1.  One
+ * workgroup, f64 accumulation.  bwd: dp = g 2(p-y)/N resp.
+ * g (p-y) / max(p(1-p), 1e-12) / N with g a device scalar (capturable). */
+#define UM_LABEL_MSE 0
+#define UM_LABEL_BCE 1
+int um_label_loss_fwd(int kind, const float* p, int N, int n_real, float* out,
+                      hipStream_t stream);
+int um_label_loss_bwd(int kind, const float* p, int N, int n_real, const float* g, float* dp,
+                      hipStream_t stream);
+/* two NCHW f32 images [N][C][H][W] -> one NHWC batch [2N][H][W][Cp] (dtype):
+ * rows 0..N-1 from a, N..2N-1 from b; padding and rounding of
+ * um_image_to_nhwc.  Replaces detach().clone() + torch.cat + the layout
+ * conversion per pyramid level in run_discriminator (reference
+ * train/utils.py:262-264).  No gradient. */
+int um_image_pair_to_nhwc(int dtype, const float* a, const float* b, int N, int C, int H, int W,
+                          int Cp, void* out, hipStream_t stream);
 
 /* ---------------------------------------------------------- evaluation ---
  * evaluate_model / sparsification (reference train/evaluate.py:66-196,

@@ -13,6 +13,14 @@
 //   um_l1_mean          mean |a - b| of two NHWC feature maps (PerceptualLoss
 //                       via train/utils.py l1_loss), last-workgroup f64 finish
 //   um_l1_mean_bwd      d/da = -d/db = g * sign(a - b) / n
+//   um_label_loss_fwd   MSELoss / BCELoss (reduction='mean') of N probabilities
+//                       against step labels y[n] = (n < n_real): the label
+//                       tensor of GeneratorLoss (ones) and run_discriminator
+//                       (ones then zeros) is never materialised
+//   um_label_loss_bwd   its gradient, the upstream scalar read from the device
+//   um_image_pair_to_nhwc  two NCHW f32 images -> one NHWC batch [2N]: the
+//                       torch.cat of run_discriminator's real and detached
+//                       recon pyramids folded into the layout conversion
 #include "common.h"
 
 namespace {
@@ -138,6 +146,92 @@ __global__ void l1_mean_bwd_kernel(const T* __restrict__ a, const T* __restrict_
   }
 }
 
+// y[n] = (n < n_real).  kind 0: (p - y)^2; kind 1: torch's BCELoss element,
+// -(y max(log p, -100) + (1 - y) max(log1p(-p), -100)).  N is a batch size:
+// the element maths runs in f64, so the result is the f64 value rounded once
+__device__ __forceinline__ double label_loss_elem(int kind, double p, bool real) {
+  if (kind == 0) {
+    const double d = p - (real ? 1.0 : 0.0);
+    return d * d;
+  }
+  const double l = real ? log(p) : log1p(-p);  // -inf at a saturated sigmoid
+  return -fmax(l, -100.0);
+}
+
+__global__ void __launch_bounds__(256) label_loss_fwd_kernel(int kind,
+                                                             const float* __restrict__ p,
+                                                             int N, int n_real,
+                                                             float* __restrict__ out) {
+  __shared__ double red[4];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < N; i += 256) s += label_loss_elem(kind, (double)p[i], i < n_real);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) out[0] = (float)(((red[0] + red[1]) + (red[2] + red[3])) / (double)N);
+}
+
+// MSE: g 2 (p - y) / N; BCE: g (p - y) / max(p (1 - p), 1e-12) / N (torch's
+// binary_cross_entropy_backward, finite at p = 0 and p = 1)
+__global__ void __launch_bounds__(256) label_loss_bwd_kernel(int kind,
+                                                             const float* __restrict__ p,
+                                                             int N, int n_real,
+                                                             const float* __restrict__ g,
+                                                             float* __restrict__ dp) {
+  const double gn = (double)g[0] / (double)N;
+  for (int i = threadIdx.x; i < N; i += 256) {
+    const double pi = (double)p[i];
+    const double d = pi - (i < n_real ? 1.0 : 0.0);
+    dp[i] = (float)(kind == 0 ? gn * 2.0 * d : gn * d / fmax(pi * (1.0 - pi), 1e-12));
+  }
+}
+
+// as misc.hip's image_to_nhwc_kernel, batch rows [0, N) from a, [N, 2N) from b
+template <typename T>
+__global__ void image_pair_to_nhwc_kernel(const float* __restrict__ a,
+                                          const float* __restrict__ b, int N, int C, int H,
+                                          int W, int Cp, T* __restrict__ out) {
+  const long total = 2L * N * H * W * Cp;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total;
+       i += (long)gridDim.x * blockDim.x) {
+    const int c = i % Cp;
+    const long pix = i / Cp;
+    const int xw = pix % W;
+    const int yh = (pix / W) % H;
+    const int n2 = pix / ((long)W * H);
+    const float* x = n2 < N ? a : b;
+    const int n = n2 < N ? n2 : n2 - N;
+    const float v = c < C ? x[(((long)n * C + c) * H + yh) * W + xw] : 0.f;
+    out[i] = from_f32<T>(v);
+  }
+}
+
+// as misc.hip's image_to_nhwc8_kernel (bf16, Cp a multiple of 8): thread =
+// (pixel, 8-channel group), planar reads coalesced, one 16-byte store
+__global__ void image_pair_to_nhwc8_kernel(const float* __restrict__ a,
+                                           const float* __restrict__ b, int N, int C, long HW,
+                                           int Cp, bf16_t* __restrict__ out) {
+  const int G = Cp / 8;
+  const long NP = 2L * N * HW;
+  const long total = NP * G;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total;
+       i += (long)gridDim.x * blockDim.x) {
+    const int g = (int)(i / NP);
+    const long pix = i - (long)g * NP;
+    const long n2 = pix / HW, p = pix - n2 * HW;
+    const float* x = n2 < N ? a : b;
+    const long n = n2 < N ? n2 : n2 - N;
+    float v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int c = g * 8 + e;
+      v[e] = c < C ? x[(n * C + c) * HW + p] : 0.f;
+    }
+    store8(out + pix * Cp + g * 8, v);
+  }
+}
+
 inline int grid_for(long n) {
   long b = (n + 255) / 256;
   if (b > 4096) b = 4096;
@@ -216,6 +310,42 @@ int um_l1_mean_bwd(int dtype, const void* a, const void* b, long n, const float*
   else
     hipLaunchKernelGGL(l1_mean_bwd_kernel<float>, dim3(gr), dim3(256), 0, st, (const float*)a,
                        (const float*)b, n, g, (float*)da, (float*)db);
+  UM_LAUNCH_CHECK();
+  return UM_OK;
+}
+
+int um_label_loss_fwd(int kind, const float* p, int N, int n_real, float* out, hipStream_t st) {
+  UM_CHECK_ARG(kind == UM_LABEL_MSE || kind == UM_LABEL_BCE, "um_label_loss_fwd: kind %d", kind);
+  UM_CHECK_ARG(p && out && N > 0 && n_real >= 0, "um_label_loss_fwd: N %d n_real %d", N, n_real);
+  hipLaunchKernelGGL(label_loss_fwd_kernel, dim3(1), dim3(256), 0, st, kind, p, N, n_real, out);
+  UM_LAUNCH_CHECK();
+  return UM_OK;
+}
+
+int um_label_loss_bwd(int kind, const float* p, int N, int n_real, const float* g, float* dp,
+                      hipStream_t st) {
+  UM_CHECK_ARG(kind == UM_LABEL_MSE || kind == UM_LABEL_BCE, "um_label_loss_bwd: kind %d", kind);
+  UM_CHECK_ARG(p && g && dp && N > 0 && n_real >= 0, "um_label_loss_bwd: N %d n_real %d", N,
+               n_real);
+  hipLaunchKernelGGL(label_loss_bwd_kernel, dim3(1), dim3(256), 0, st, kind, p, N, n_real, g, dp);
+  UM_LAUNCH_CHECK();
+  return UM_OK;
+}
+
+int um_image_pair_to_nhwc(int dtype, const float* a, const float* b, int N, int C, int H, int W,
+                          int Cp, void* out, hipStream_t st) {
+  UM_CHECK_ARG(a && b && out && N > 0 && C > 0 && H > 0 && W > 0 && C <= Cp,
+               "um_image_pair_to_nhwc: N %d C %d H %d W %d Cp %d", N, C, H, W, Cp);
+  const long total = 2L * N * H * W * Cp;
+  if (dtype == UM_BF16 && Cp % 8 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0)
+    hipLaunchKernelGGL(image_pair_to_nhwc8_kernel, dim3(grid_for(total / 8)), dim3(256), 0, st, a,
+                       b, N, C, (long)H * W, Cp, (bf16_t*)out);
+  else if (dtype == UM_BF16)
+    hipLaunchKernelGGL(image_pair_to_nhwc_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, st,
+                       a, b, N, C, H, W, Cp, (bf16_t*)out);
+  else
+    hipLaunchKernelGGL(image_pair_to_nhwc_kernel<float>, dim3(grid_for(total)), dim3(256), 0, st,
+                       a, b, N, C, H, W, Cp, (float*)out);
   UM_LAUNCH_CHECK();
   return UM_OK;
 }

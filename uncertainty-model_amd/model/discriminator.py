@@ -41,12 +41,22 @@ class RandomDiscriminator(nn.Module):
         self.compute_dtype = umamd.resolve_dtype(dtype)
         self._packer = P.WeightPacker()
 
-    def _features(self, pyramid: ImagePyramid) -> List[Tensor]:
-        """NHWC feature maps of the stages (reference :53-76)."""
+    # a pyramid level may be a pair (a, b) of equal-shape images: the batch
+    # cat((a, b), 0) without the cat (train.utils.run_discriminator)
+    accepts_image_pairs = True
+
+    def _features(self, pyramid) -> List[Tensor]:
+        """NHWC feature maps of the stages (reference :53-76).  Each level is
+        an image tensor or a pair of them (no gradient), see above."""
         feats = []
         out = None
         for i, (images, layer) in enumerate(zip(pyramid, self.layers)):
-            img = D.image_to_nhwc(images, self.compute_dtype)
+            if isinstance(images, (tuple, list)):
+                first, second = images
+                img = D.image_pair_to_nhwc(first, second, self.compute_dtype)
+                images = first
+            else:
+                img = D.image_to_nhwc(images, self.compute_dtype)
             if i == 0:
                 x = img
             else:

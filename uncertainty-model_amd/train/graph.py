@@ -11,6 +11,24 @@ replays it:
   graph 2: fused Adam over those gradients (pointer table uploaded once,
            step counter and lr read from device memory by the kernel)
 
+With a discriminator (``disc=...``: the adversarial step, reference
+train/train.py:116-149) the same order as train.train.train_step, in three
+graphs:
+
+  graph 1: as above, the loss with the generator and perceptual terms
+           through ``disc_clone`` (frozen: no weight-gradient launches, no
+           ``.grad`` that a replay could accumulate into)
+  graph 2: model Adam, then run_discriminator forward + backward on the
+           recon pyramid of graph 1's forward (read in place)
+  graph 3: discriminator Adam
+
+The perceptual term is captured always and multiplied by a device scalar
+gate (0.0 / 1.0) that ``cap(left, right, perceptual=bool)`` fills before the
+replay: the reference switches the term on after ``perceptual_start``
+batches of every epoch, and one capture serves both sides.  The clone is
+refreshed in place by the caller (``disc_clone.load_state_dict(
+disc.state_dict())``), never replaced: the graphs hold its addresses.
+
 Construction runs ``warmup`` eager steps (allocator warm-up, optimiser state
 creation) and then captures; by default (``restore_state=True``) the
 parameters, BN buffers and Adam moments / step counters are put back to their
@@ -54,8 +72,15 @@ from . import utils as u
 class CapturedTrainStep:
     def __init__(self, model, loss_function, optimiser, left, right, scale: float,
                  scales: int = 4, warmup: int = 3, restore_state: bool = True,
-                 stream=None):
-        """``stream``: the stream to warm up and capture on (default: a new
+                 stream=None, disc=None, disc_optimiser=None, disc_loss_function=None,
+                 disc_clone=None, batch_size=None):
+        """``disc``, ``disc_optimiser`` (umamd.optim.Adam), ``disc_loss_function``
+        and ``disc_clone`` (a copy of ``disc`` the caller refreshes in place;
+        its parameters are frozen here): capture the adversarial step, see
+        the module docstring.  ``batch_size``: the loader's batch size, which
+        run_discriminator labels by (default: this batch's size).
+
+        ``stream``: the stream to warm up and capture on (default: a new
         one).  A DistributedDataParallel model must have been constructed
         while that stream was current: DDP keeps the parameters'
         AccumulateGrad nodes alive, and a node created on another stream
@@ -90,7 +115,33 @@ class CapturedTrainStep:
         self._comm = None
         if self.group is not None and dist.get_backend(self.group) == 'nccl':
             self._comm = rccl.acquire(self.group)
-        snap = self._snapshot(model, optimiser) if restore_state else None
+        self.disc, self.disc_optimiser, self.disc_clone = disc, disc_optimiser, disc_clone
+        self.disc_loss_function = disc_loss_function
+        self.batch_size = int(batch_size) if batch_size is not None else int(left.shape[0])
+        if disc is not None:
+            from .loss import TukraUncertaintyLoss
+            if self.group is not None:
+                raise NotImplementedError('CapturedTrainStep: the adversarial step is not '
+                                          'captured under data parallel (step eagerly)')
+            if disc_clone is None or disc_optimiser is None or disc_loss_function is None:
+                raise TypeError('CapturedTrainStep with disc needs disc_optimiser, '
+                                'disc_loss_function and disc_clone')
+            if not hasattr(disc_optimiser, 'prepare'):
+                raise TypeError('CapturedTrainStep needs umamd.optim.Adam for the discriminator')
+            if not isinstance(loss_function, TukraUncertaintyLoss):
+                raise TypeError('CapturedTrainStep with disc needs TukraUncertaintyLoss '
+                                '(the gated perceptual term)')
+            # the clone is never stepped (reference train.py:112,150-152): frozen,
+            # the gradient still reaches the recon and nothing accumulates
+            for p in disc_clone.parameters():
+                p.requires_grad_(False)
+                p.grad = None
+        snap = None
+        if restore_state:
+            snap = [(model, optimiser, self._snapshot(model, optimiser))]
+            if disc is not None:
+                snap.append((disc, disc_optimiser, self._snapshot(disc, disc_optimiser)))
+                snap.append((disc_clone, None, self._snapshot(disc_clone, None)))
         self.model, self.loss_function, self.optimiser = model, loss_function, optimiser
         self.scale, self.scales = float(scale), scales
         # weight gradients on a side stream beside the dgrad chain (umamd.overlap);
@@ -103,6 +154,13 @@ class CapturedTrainStep:
         # made once: no add and no ones-fill launch inside the step
         self._seed = torch.ones((), dtype=torch.float32, device=left.device)
         self.right = right.detach().clone().contiguous()
+        # the perceptual gate (see the module docstring); 1.0 through warm-up
+        # and capture so every buffer of the term exists
+        self._gate = torch.ones((), dtype=torch.float32, device=left.device) \
+            if disc is not None else None
+        self._gate_host = True
+        self._pyramid = self._recon = None
+        self.disc_loss = None
         cur = torch.cuda.current_stream()
         side = stream if stream is not None else torch.cuda.Stream()
         if side != cur:
@@ -112,9 +170,15 @@ class CapturedTrainStep:
                 optimiser.zero_grad(set_to_none=True)
                 self._fwd_bwd()
                 optimiser.step()
+                if disc is not None:
+                    disc_optimiser.zero_grad(set_to_none=True)
+                    self._disc_fwd_bwd()
+                    disc_optimiser.step()
         cur.wait_stream(side)
         torch.cuda.synchronize()
         optimiser.zero_grad(set_to_none=True)
+        if disc is not None:
+            disc_optimiser.zero_grad(set_to_none=True)
         # capture on the warm-up stream so autograd's cached AccumulateGrad
         # nodes see the stream they were created on; the backward (autograd's
         # device thread) launches into the capture too.
@@ -147,14 +211,28 @@ class CapturedTrainStep:
         with torch.cuda.graph(self.g_opt, pool=self.g_fb.pool(), stream=side,
                               capture_error_mode=mode):
             optimiser.step()
+            if disc is not None:  # on the recon pyramid graph 1 left in the pool
+                self.disc_loss = self._disc_fwd_bwd().detach()
+        self.g_dopt = None
+        if disc is not None:
+            disc_optimiser.prepare()
+            self._opt_tables += list(getattr(disc_optimiser, '_tables', {}).values())
+            torch.cuda.synchronize()
+            self.g_dopt = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.g_dopt, pool=self.g_fb.pool(), stream=side,
+                                  capture_error_mode=mode):
+                disc_optimiser.step()
         if snap is not None:
-            self._restore(model, optimiser, snap)
+            for mod, opt, sn in snap:
+                self._restore(mod, opt, sn)
 
     @staticmethod
     @torch.no_grad()
     def _snapshot(model, opt):
         params = [p.detach().clone() for p in model.parameters()]
         bufs = [b.detach().clone() for b in model.buffers()]
+        if opt is None:  # a module without optimiser (the discriminator clone)
+            return params, bufs, {}, {}
         moments = {id(p): {k: v.clone() for k, v in opt.state[p].items() if torch.is_tensor(v)}
                    for g in opt.param_groups for p in g['params'] if p in opt.state}
         dev = {gi: st['step'].clone() for gi, st in opt._dev.items()}
@@ -170,6 +248,9 @@ class CapturedTrainStep:
             p.copy_(v)
         for b, v in zip(model.buffers(), bufs):
             b.copy_(v)
+        if opt is None:
+            torch.cuda.synchronize()
+            return
         for g in opt.param_groups:
             for p in g['params']:
                 for k, v in opt.state.get(p, {}).items():
@@ -191,7 +272,14 @@ class CapturedTrainStep:
                 recon = u.reconstruct_pyramid(disparities, pyramid)
         else:
             recon = u.reconstruct_pyramid(disparities, pyramid)
-        disp_loss, error_loss = self.loss_function(pyramid, disparities, recon, 0, None)
+        if self.disc is not None:
+            disp_loss, error_loss = self.loss_function._forward(
+                pyramid, disparities, recon, 0, self.disc_clone, gate=self._gate)
+            # read in place by _disc_fwd_bwd; detached, so that no autograd graph
+            # (and none of its AccumulateGrad nodes) outlives the backward
+            self._pyramid, self._recon = pyramid, [r.detach() for r in recon]
+        else:
+            disp_loss, error_loss = self.loss_function(pyramid, disparities, recon, 0, None)
 
         def backward():
             seeds = tuple(self._seed if t.dtype == self._seed.dtype and t.dim() == 0
@@ -209,6 +297,16 @@ class CapturedTrainStep:
         if self._buckets is not None:
             self._reduce_grads()
         return disp_loss, error_loss
+
+    def _disc_fwd_bwd(self):
+        """the discriminator's own step up to its gradients (train_step:
+        run_discriminator + backward), on the pyramids of the last _fwd_bwd"""
+        disc_loss = u.run_discriminator(self._pyramid, self._recon, self.disc,
+                                        self.disc_loss_function, self.batch_size)
+        seed = self._seed if disc_loss.dtype == self._seed.dtype and disc_loss.dim() == 0 \
+            else torch.ones_like(disc_loss)
+        torch.autograd.backward((disc_loss,), (seed,))
+        return disc_loss
 
     @property
     def _flat(self):
@@ -232,14 +330,23 @@ class CapturedTrainStep:
         if self._buckets is not None:
             self._buckets.remove()
             self._buckets = None
-        self.g_fb = self.g_opt = None
+        self.g_fb = self.g_opt = self.g_dopt = None
+        self._pyramid = self._recon = None
         self._opt_tables = []
         if self._comm is not None:  # after the graphs that recorded its collectives
             self._comm.sync()
             rccl.release(self._comm)
             self._comm = None
 
-    def __call__(self, left=None, right=None):
+    def __call__(self, left=None, right=None, perceptual: bool = False):
+        """Replay one step.  Without a discriminator -> (disp_loss,
+        error_loss); with one -> (disp_loss, error_loss, disc_loss), and
+        ``perceptual`` sets the perceptual term's gate (the reference turns
+        the term on from batch ``perceptual_start`` of every epoch).  The
+        returned tensors are static graph outputs, detached."""
+        if self._gate is not None and bool(perceptual) != self._gate_host:
+            self._gate.fill_(1.0 if perceptual else 0.0)
+            self._gate_host = bool(perceptual)
         if left is not None:
             self.left.copy_(left)
         if right is not None:
@@ -248,4 +355,7 @@ class CapturedTrainStep:
             self._comm.note_stream(torch.cuda.current_stream())
         self.g_fb.replay()
         self.g_opt.replay()
+        if self.g_dopt is not None:
+            self.g_dopt.replay()
+            return self.disp_loss, self.error_loss, self.disc_loss
         return self.disp_loss, self.error_loss

@@ -94,7 +94,10 @@ class PerceptualLoss(nn.Module):
 class GeneratorLoss(nn.Module):
     """Loss of failing to convince the discriminator (reference :308-337):
     ``self.adversarial`` (MSE or BCE) of the discriminator's predictions on
-    the reconstructions against ones."""
+    the reconstructions against ones.  With exactly nn.MSELoss / nn.BCELoss
+    (mean reduction, no weight) on device predictions the loss and its
+    gradient are one um_label_loss launch each and the ones tensor is never
+    made; any other ``adversarial`` module takes the ATen path."""
 
     def __init__(self, loss: str = 'mse') -> None:
         super().__init__()
@@ -102,6 +105,9 @@ class GeneratorLoss(nn.Module):
 
     def forward(self, recon_pyramid: ImagePyramid, discriminator: Module) -> Tensor:
         predictions = discriminator(recon_pyramid)
+        kind = DF.label_loss_kind(self.adversarial)
+        if kind is not None and predictions.is_cuda:
+            return DF.label_loss(predictions, kind, predictions.numel())
         labels = torch.ones_like(predictions)
         return self.adversarial(predictions, labels)
 
@@ -161,6 +167,17 @@ class TukraUncertaintyLoss(nn.Module):
     def forward(self, image_pyramid: ImagePyramid, predictions: ImagePyramid,
                 recon_pyramid: ImagePyramid, epoch: Optional[int] = None,
                 discriminator: Optional[Module] = None):
+        return self._forward(image_pyramid, predictions, recon_pyramid, epoch, discriminator)
+
+    def _forward(self, image_pyramid: ImagePyramid, predictions: ImagePyramid,
+                 recon_pyramid: ImagePyramid, epoch: Optional[int] = None,
+                 discriminator: Optional[Module] = None, gate: Optional[Tensor] = None):
+        """``forward``; with ``gate`` (a 0-dim device tensor holding 0.0 or
+        1.0: train.graph.CapturedTrainStep) the perceptual term is always
+        evaluated and multiplied by it instead of being switched by
+        ``epoch``, so one captured graph serves both sides of
+        ``perceptual_start``.  gate 1.0 leaves the term's value and gradient
+        bits unchanged; gate 0.0 makes them exact zeros (finite terms)."""
         for p, im, r in zip(predictions, image_pyramid, recon_pyramid):
             tag = getattr(r, '_umamd_recon', None)
             if tag is None or tag != (id(p), id(im)):
@@ -181,7 +198,10 @@ class TukraUncertaintyLoss(nn.Module):
             # the gradient back to the disparities through the warp adjoint
             adversarial_loss = self.adversarial(recon_pyramid, discriminator)
             disp_loss = disp_loss + adversarial_loss * self.adversarial_weight
-            if epoch is not None and epoch >= self.perceptual_start:
+            if gate is not None:
+                perceptual_loss = self.perceptual(image_pyramid, recon_pyramid, discriminator)
+                disp_loss = disp_loss + perceptual_loss * self.perceptual_weight * gate
+            elif epoch is not None and epoch >= self.perceptual_start:
                 perceptual_loss = self.perceptual(image_pyramid, recon_pyramid, discriminator)
                 disp_loss = disp_loss + perceptual_loss * self.perceptual_weight
         return disp_loss, error_loss

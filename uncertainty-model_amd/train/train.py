@@ -91,11 +91,21 @@ class _GraphSteps:
     batch of another shape (a ragged last batch) takes one eager step.
 
     Used when the model's parameters are on a HIP device, the optimiser is
-    umamd.optim.Adam, the loss is the fused umamd loss and there is no
-    discriminator (the adversarial step stays eager).  A DistributedDataParallel
-    model must have been built by train.parallel.data_parallel (which builds it
-    under the capture stream, see there); a DDP built elsewhere steps eagerly.
-    UMAMD_TRAIN_GRAPH=0 turns it off."""
+    umamd.optim.Adam and the loss is the fused umamd loss.  A
+    DistributedDataParallel model must have been built by
+    train.parallel.data_parallel (which builds it under the capture stream, see
+    there); a DDP built elsewhere steps eagerly.  UMAMD_TRAIN_GRAPH=0 turns it
+    off.
+
+    The adversarial step (a discriminator is passed) is captured too when the
+    discriminator and its umamd.optim.Adam are on the HIP device and the model
+    is not data-parallel (DDP + discriminator steps eagerly);
+    UMAMD_ADV_GRAPH=0 keeps it eager.  The reference's per-epoch
+    ``deepcopy(disc)`` becomes ONE persistent clone owned here (the graphs
+    hold its addresses), refreshed in place by ``load_state_dict`` at epoch
+    start -- the values a fresh deepcopy would have -- and every
+    ``perceptual_update_freq`` batches; the ragged-batch eager step uses the
+    same clone."""
 
     def __init__(self, model, loss_function, optimiser, scales):
         self.model, self.loss_function, self.optimiser = model, loss_function, optimiser
@@ -103,6 +113,30 @@ class _GraphSteps:
         self.key = None
         self.cap = None
         self._stream = None
+        self.disc = self.disc_optimiser = self.disc_loss_function = self.disc_clone = None
+        self.batch_size = None
+        # how often the step was captured / replayed / handed back for an eager step
+        self.captures = self.replays = self.eager_steps = 0
+
+    def bind_discriminator(self, disc, disc_optimiser, disc_loss_function, batch_size):
+        """Epoch start of an adversarial loop: -> the persistent clone holding
+        ``disc``'s current state (what the reference's deepcopy would hold);
+        ``disc=None``: a plain loop, -> None."""
+        if disc is not self.disc:
+            self.release()
+            self.disc = disc
+            self.disc_clone = deepcopy(disc) if disc is not None else None
+        elif disc is not None:
+            self.disc_clone.load_state_dict(disc.state_dict())
+        self.disc_optimiser, self.disc_loss_function = disc_optimiser, disc_loss_function
+        self.batch_size = batch_size
+        return self.disc_clone
+
+    def release(self):
+        """drop the captured graphs (``close()`` of the step) and the key"""
+        if self.cap is not None:
+            self.cap.close()
+        self.cap = self.key = None
 
     @property
     def stream(self):
@@ -117,10 +151,19 @@ class _GraphSteps:
         return self._stream
 
     @staticmethod
-    def usable(model, loss_function, optimiser, disc) -> bool:
+    def usable(model, loss_function, optimiser, disc, disc_optimiser=None) -> bool:
         from torch.nn.parallel import DistributedDataParallel
-        if os.environ.get('UMAMD_TRAIN_GRAPH', '1') == '0' or disc is not None:
+        if os.environ.get('UMAMD_TRAIN_GRAPH', '1') == '0':
             return False
+        if disc is not None:
+            if os.environ.get('UMAMD_ADV_GRAPH', '1') == '0':
+                return False
+            dp = next(disc.parameters(), None)
+            if dp is None or not dp.is_cuda or not isinstance(disc_optimiser, Adam):
+                return False
+            if isinstance(model, DistributedDataParallel) or \
+                    isinstance(disc, DistributedDataParallel):
+                return False  # data-parallel adversarial steps stay eager
         if not hasattr(optimiser, 'sync_lr') or not _fused_loss(loss_function):
             return False
         p = next(model.parameters(), None)
@@ -133,20 +176,37 @@ class _GraphSteps:
                 return False  # a gloo all-reduce cannot be captured
         return True
 
-    def __call__(self, left, right, scale):
+    def __call__(self, left, right, scale, perceptual: bool = False):
         from .graph import CapturedTrainStep
         key = (float(scale), tuple(left.shape), tuple(right.shape), left.dtype)
-        if self.cap is not None and self.key != key and self.key[1:] != key[1:]:
+        if self.disc is not None:
+            # after the batch shape (another shape = an eager step, below)
+            key += (id(self.disc), id(self.disc_optimiser), id(self.disc_loss_function),
+                    self.batch_size)
+        if self.cap is not None and self.key != key and self.key[1:4] != key[1:4]:
+            self.eager_steps += 1
             return None  # another batch shape: the caller steps eagerly
         self.optimiser.sync_lr()
+        if self.disc is not None:
+            self.disc_optimiser.sync_lr()
         if self.key != key:
             if self.cap is not None:  # scale changed: drop the old graphs before capturing
                 self.cap.close()
             self.cap = None
             torch.cuda.synchronize()
+            adv = {}
+            if self.disc is not None:
+                adv = dict(disc=self.disc, disc_optimiser=self.disc_optimiser,
+                           disc_loss_function=self.disc_loss_function,
+                           disc_clone=self.disc_clone, batch_size=self.batch_size)
             self.cap = CapturedTrainStep(self.model, self.loss_function, self.optimiser, left,
-                                         right, scale, scales=self.scales, stream=self.stream)
+                                         right, scale, scales=self.scales, stream=self.stream,
+                                         **adv)
             self.key = key
+            self.captures += 1
+        self.replays += 1
+        if self.disc is not None:
+            return self.cap(left, right, perceptual=perceptual)
         return self.cap(left, right)
 
 
@@ -168,20 +228,30 @@ def train_one_epoch(model: Module, loader: DataLoader, loss_function: Module,
     disp_loss_per_image = unc_loss_per_image = disc_loss_per_image = None
     batch_size = loader.batch_size if loader.batch_size is not None else len(loader)
     description = f'Epoch #{epoch_number}' if epoch_number is not None else 'Epoch'
-    disc_clone = deepcopy(disc) if disc is not None else None
     graphs = None
     if graph_steps is not None and _GraphSteps.usable(model, loss_function, model_optimiser,
-                                                      disc):
+                                                      disc, disc_optimiser):
         graphs = graph_steps
+    if graphs is not None:
+        # the captured adversarial step: one persistent clone, refreshed in place
+        disc_clone = graphs.bind_discriminator(disc, disc_optimiser, disc_loss_function,
+                                               batch_size)
+    else:
+        disc_clone = deepcopy(disc) if disc is not None else None
+    perceptual_start = getattr(loss_function, 'perceptual_start', 0)
     it = tqdm.tqdm(loader, description, unit='batch', disable=(no_pbar or rank > 0)) \
         if tqdm is not None else loader
     for i, image_pair in enumerate(it):
         # a DeviceAugment batch (uint8 + draws) is resized / augmented on the GPU
         left, right = to_device(image_pair, device)
-        out = graphs(left, right, scale) if graphs is not None else None
+        if graphs is None:
+            out = None
+        elif disc is None:  # the plain step: the call of the loop without a discriminator
+            out = graphs(left, right, scale)
+        else:  # the reference passes the batch index as the loss's ``epoch``
+            out = graphs(left, right, scale, perceptual=i >= perceptual_start)
         if out is not None:
-            disp_loss, error_loss = out
-            disc_loss = None
+            disp_loss, error_loss, disc_loss = out if len(out) == 3 else (*out, None)
         elif graphs is not None:
             # a batch of another shape: one eager step on the loop's capture
             # stream (see _GraphSteps.stream)

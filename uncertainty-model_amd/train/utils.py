@@ -15,6 +15,7 @@ import torch
 from torch import Tensor
 from torch.optim import Optimizer
 
+from umamd import discfn as DF
 from umamd import lossfn as LF
 
 Device = Union[torch.device, str]
@@ -90,10 +91,26 @@ def adjust_learning_rate(optimiser: Optimizer, epoch: int, lr: float,
 def run_discriminator(image_pyramid: ImagePyramid, recon_pyramid: ImagePyramid,
                       discriminator, disc_loss_function, batch_size: int) -> Tensor:
     """Discriminator predictions on real (label 1) and detached reconstructed
-    (label 0) pyramids and its loss / 2 (reference :248-273)."""
-    recon_pyramid = detach_pyramid(recon_pyramid)
-    pyramid = concatenate_pyramids(image_pyramid, recon_pyramid)
+    (label 0) pyramids and its loss / 2 (reference :248-273).
+
+    A umamd RandomDiscriminator reads each level's image and detached recon
+    in place (um_image_pair_to_nhwc: no clone, no cat), and exactly
+    nn.MSELoss / nn.BCELoss (mean reduction, no weight) is one um_label_loss
+    launch against labels that are never materialised; any other
+    discriminator or loss module takes the clone + cat + ATen path."""
+    from torch.nn.parallel import DistributedDataParallel
+    d = discriminator.module if isinstance(discriminator, DistributedDataParallel) \
+        else discriminator
+    if getattr(d, 'accepts_image_pairs', False) and image_pyramid[0].is_cuda:
+        # the pair conversion has no gradient (it raises on an input that requires one)
+        pyramid = [(im, r.detach()) for im, r in zip(image_pyramid, recon_pyramid)]
+    else:
+        recon_pyramid = detach_pyramid(recon_pyramid)
+        pyramid = concatenate_pyramids(image_pyramid, recon_pyramid)
     predictions = discriminator(pyramid)
+    kind = DF.label_loss_kind(disc_loss_function)
+    if kind is not None and predictions.is_cuda:
+        return DF.label_loss(predictions, kind, batch_size) / 2
     labels = torch.zeros_like(predictions)
     labels[:batch_size] = 1
     return disc_loss_function(predictions, labels) / 2

@@ -22,6 +22,7 @@ PAD_ZERO, PAD_REFLECT = 0, 1
 EPI_NONE, EPI_STATS, EPI_SIGMOID_SCALE, EPI_RESIDUAL, EPI_STAT_SLOTS = 0, 1, 2, 3, 4
 STAT_SLOTS = 16  # UM_STAT_SLOTS (include/umamd.h)
 CAT_COPY, CAT_UP2, CAT_PSHUF = 0, 1, 2
+LABEL_MSE, LABEL_BCE = 0, 1  # UM_LABEL_* (include/umamd.h)
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -156,6 +157,9 @@ _SIG = {
     'um_l1_mean_ws': (_L, []),
     'um_l1_mean': (_I, [_I, _P, _P, _L, _P, _P, 's']),
     'um_l1_mean_bwd': (_I, [_I, _P, _P, _L, _P, _P, _P, 's']),
+    'um_label_loss_fwd': (_I, [_I, _P, _I, _I, _P, 's']),
+    'um_label_loss_bwd': (_I, [_I, _P, _I, _I, _P, _P, 's']),
+    'um_image_pair_to_nhwc': (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _P, 's']),
     'um_ssim_ws': (_L, [_I, _I, _I]),
     'um_ssim_gauss': (_I, [_P, _P, _I, _I, _I, _I, _F, _F, _P, _P, 's']),
     'um_avgpool_valid': (_I, [_P, _I, _I, _I, _I, _P, 's']),

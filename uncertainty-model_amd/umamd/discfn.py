@@ -6,6 +6,11 @@
                        flows back to the disparities through the warp)
   * ``disc_head``      sigmoid(Linear(flatten(x))) on the last NHWC feature map
   * ``l1_mean``        mean |a - b| of two NHWC feature maps (PerceptualLoss)
+  * ``label_loss``     MSELoss / BCELoss of the predictions against step labels
+                       that are never materialised (GeneratorLoss: all ones;
+                       run_discriminator: ones then zeros)
+  * ``image_pair_to_nhwc``  two NCHW images -> one NHWC batch, no gradient
+                       (run_discriminator's real + detached recon levels)
 """
 from __future__ import annotations
 
@@ -40,6 +45,27 @@ def image_to_nhwc(img: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     return ImageToNHWCFn.apply(img, dtype)
 
 
+def image_pair_to_nhwc(a: torch.Tensor, b: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """[N,C,H,W] f32 x 2 -> NHWC [2N,H,W,ceil8(C)] in ``dtype``: what
+    ``image_to_nhwc(torch.cat((a, b), 0), dtype)`` gives, without the cat.
+    No autograd: the inputs must not require grad (pass ``.detach()``)."""
+    L.require_device(a)
+    L.require_device(b)
+    if a.requires_grad or b.requires_grad:
+        raise L.UmamdError('image_pair_to_nhwc has no gradient: detach the inputs')
+    if a.shape != b.shape or a.dim() != 4:
+        raise L.UmamdError(f'image_pair_to_nhwc: {tuple(a.shape)} vs {tuple(b.shape)}')
+    if a.dtype != torch.float32 or not a.is_contiguous():
+        a = a.float().contiguous()
+    if b.dtype != torch.float32 or not b.is_contiguous():
+        b = b.float().contiguous()
+    N, C, H, W = a.shape
+    Cp = U.ceil8(C)
+    out = torch.empty((2 * N, H, W, Cp), dtype=dtype, device=a.device)
+    call('um_image_pair_to_nhwc', L.dtype_code(dtype), ptr(a), ptr(b), N, C, H, W, Cp, ptr(out))
+    return out
+
+
 class DiscHeadFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias):
@@ -63,8 +89,13 @@ class DiscHeadFn(torch.autograd.Function):
         N, H, W, C = xc.shape
         dp = dprob.float().contiguous()
         dx = torch.empty_like(xc) if ctx.needs_input_grad[0] else None
-        dw = torch.empty((1, H * W * C), dtype=torch.float32, device=xc.device)
-        db = torch.empty((1,), dtype=torch.float32, device=xc.device)
+        # a frozen head (the adversarial step's discriminator clone): no dw / db
+        dw = torch.empty((1, H * W * C), dtype=torch.float32, device=xc.device) \
+            if ctx.needs_input_grad[1] else None
+        db = torch.empty((1,), dtype=torch.float32, device=xc.device) \
+            if ctx.needs_input_grad[2] else None
+        if dx is None and dw is None and db is None:
+            return None, None, None
         call('um_disc_head_bwd', L.dtype_code(xc.dtype), ptr(xc), N, H * W, C, ptr(w), ptr(prob),
              ptr(dp), ptr(dx), ptr(dw), ptr(db))
         return dx, dw, db
@@ -100,3 +131,46 @@ class L1MeanFn(torch.autograd.Function):
 
 def l1_mean(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return L1MeanFn.apply(a, b)
+
+
+class LabelLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, prob, kind, n_real):
+        L.require_device(prob)
+        p = prob.detach()
+        if p.dtype != torch.float32 or not p.is_contiguous():
+            p = p.float().contiguous()
+        out = torch.empty((), dtype=torch.float32, device=p.device)
+        call('um_label_loss_fwd', kind, ptr(p), p.numel(), n_real, ptr(out))
+        ctx.kind, ctx.n_real = kind, n_real
+        ctx.in_dtype = prob.dtype
+        ctx.save_for_backward(p)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        p, = ctx.saved_tensors
+        gc = g.float().reshape(1).contiguous()
+        dp = torch.empty_like(p)
+        call('um_label_loss_bwd', ctx.kind, ptr(p), p.numel(), ctx.n_real, ptr(gc), ptr(dp))
+        return dp.to(ctx.in_dtype), None, None
+
+
+def label_loss_kind(loss_module):
+    """LABEL_MSE / LABEL_BCE when ``loss_module`` is exactly nn.MSELoss or
+    nn.BCELoss with reduction='mean' (and no weight), which is what
+    um_label_loss computes; None for anything else (a subclass, another
+    reduction, a weighted BCE), which keeps the ATen path."""
+    if getattr(loss_module, 'reduction', None) != 'mean':
+        return None
+    if type(loss_module) is torch.nn.MSELoss:
+        return L.LABEL_MSE
+    if type(loss_module) is torch.nn.BCELoss and loss_module.weight is None:
+        return L.LABEL_BCE
+    return None
+
+
+def label_loss(prob: torch.Tensor, kind: int, n_real: int) -> torch.Tensor:
+    """mean loss of the probabilities ``prob`` (any shape, read flat) against
+    labels 1 for the first ``n_real`` and 0 for the rest"""
+    return LabelLossFn.apply(prob, int(kind), int(max(0, min(n_real, prob.numel()))))

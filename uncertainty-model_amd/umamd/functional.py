@@ -713,8 +713,10 @@ def _cbe_fwd(x, weight, bias, gamma, beta, w1, w2, spec: ConvSpec, merge=None, y
 
 
 def _cbe_bwd(ctx, da, ds=None, need_x=True, need_b=True, dx=None, dx_accumulate=False,
-             conv_bwd=None):
+             conv_bwd=None, need_w=True):
     """Backward of _cbe_fwd -> (dx, dW, dbias, dgamma, dbeta, dw1, dw2).
+    ``need_w=False`` (a frozen conv weight, e.g. the discriminator clone of
+    the captured adversarial step): no weight-gradient launch, dW is None.
     ``dx``: write (or with ``dx_accumulate`` add) the input gradient into
     this tensor instead of a new one (a GraphBlockFn predecessor's gradient
     buffer)."""
@@ -825,9 +827,11 @@ def _cbe_bwd(ctx, da, ds=None, need_x=True, need_b=True, dx=None, dx_accumulate=
     if conv_bwd is not None:  # the caller's conv part (skip_conv_bn_elu): dy -> (dx, dW)
         dx, dW = conv_bwd(dy)
         need_x = False
-    else:
+    elif need_w:
         dW = _conv_wgrad(x, dy, K, K, Creal, R, spec.stride, spec.pad, spec.pad_mode,
                          segs=spec.segs)
+    else:
+        dW = None
     if reduce_b:
         dbias = torch.empty(K, dtype=torch.float32, device=dev)
         _reduce_rows(bparts, nbp, K, dbias)
@@ -856,8 +860,8 @@ class ConvBNELUFn(torch.autograd.Function):
         st.saved = ctx.saved_tensors
         tgt = _slot(ctx, 0) if ctx.needs_input_grad[0] else None
         dx, *rest = _cbe_bwd(st, da, ds, need_x=ctx.needs_input_grad[0],
-                             need_b=ctx.needs_input_grad[2], dx=tgt,
-                             dx_accumulate=tgt is not None)
+                             need_b=ctx.needs_input_grad[2], need_w=ctx.needs_input_grad[1],
+                             dx=tgt, dx_accumulate=tgt is not None)
         st.saved = None
         return (_give(ctx, 0, dx), *rest, None)
 
@@ -1204,20 +1208,22 @@ class GraphBlockFn(torch.autograd.Function):
             o, n = gs.slices[j]
             g = da.pop(j)
             st = states[j]
+            cw = ctx.needs_input_grad[2 + o]  # this node's conv weight (frozen: no wgrad)
             if not preds:
                 if need_x:
                     dx, *pg = _cbe_bwd(st, g, None, True, True, dx=dx_stage,
-                                       dx_accumulate=dx_stage is not None)
+                                       dx_accumulate=dx_stage is not None, need_w=cw)
                     dx_stage = dx
                 else:
-                    _, *pg = _cbe_bwd(st, g, None, False, True)
+                    _, *pg = _cbe_bwd(st, g, None, False, True, need_w=cw)
             elif len(preds) == 1:
                 p = preds[0]
                 acc = p in da
-                dx, *pg = _cbe_bwd(st, g, None, True, True, dx=da.get(p), dx_accumulate=acc)
+                dx, *pg = _cbe_bwd(st, g, None, True, True, dx=da.get(p), dx_accumulate=acc,
+                                   need_w=cw)
                 da[p] = dx
             else:
-                dm, *pg = _cbe_bwd(st, g, None, True, True)
+                dm, *pg = _cbe_bwd(st, g, None, True, True, need_w=cw)
                 k = len(preds)
                 acc = [int(p in da) for p in preds]
                 for p in preds:
@@ -1341,8 +1347,11 @@ class AttentionFn(torch.autograd.Function):
         dt = x.dtype
         dout = dout.contiguous()
         datt = _conv_dgrad(dout, wrT, (N, H, W, C), C, 1, 1, 0, L.PAD_ZERO)
-        dwr = _conv_wgrad(att, dout, C, C, C, 1, 1, 0, L.PAD_ZERO)
-        dbr = _colsum_grad(dout, C)
+        # frozen projections (the adversarial step's discriminator clone): no
+        # weight / bias gradient launches
+        need_r, need_qkv = any(ctx.needs_input_grad[7:9]), any(ctx.needs_input_grad[1:7])
+        dwr = _conv_wgrad(att, dout, C, C, C, 1, 1, 0, L.PAD_ZERO) if need_r else None
+        dbr = _colsum_grad(dout, C) if need_r else None
         dqkv = torch.empty((N, H, W, 3 * C), dtype=dt, device=dev)
         dks = torch.empty((N * S, C), dtype=torch.float32, device=dev)
         ws = torch.empty(query('um_attn_ws_tiles', N, S, C, heads), dtype=torch.float32,
@@ -1352,8 +1361,9 @@ class AttentionFn(torch.autograd.Function):
         call('um_attn_bwd', L.dtype_code(dt), N, S, C, heads, ptr(qkv), 3 * C, ptr(kmax),
              ptr(ksum), ptr(ctxm), ptr(datt), C, ptr(dqkv), 3 * C, ptr(dks), ptr(ws), ptr(dctx),
              ptr(r))
-        dwqkv = _conv_wgrad(x, dqkv, 3 * C, 3 * C, C, 1, 1, 0, L.PAD_ZERO)
-        dbqkv = _colsum_grad(dqkv, 3 * C)
+        if need_qkv:
+            dwqkv = _conv_wgrad(x, dqkv, 3 * C, 3 * C, C, 1, 1, 0, L.PAD_ZERO)
+            dbqkv = _colsum_grad(dqkv, 3 * C)
         if dout.dtype == dt:
             # dx = dout (the residual path) + the K/Q/V convs' input gradient:
             # wT [C][3C] is the weight of a 3C -> C 1x1 conv, so this is one
@@ -1364,6 +1374,8 @@ class AttentionFn(torch.autograd.Function):
             dx = dout.to(dt)
             _conv_dgrad(dqkv, wT, (N, H, W, C), 3 * C, 1, 1, 0, L.PAD_ZERO, dx=dx,
                         accumulate=True)
+        if not need_qkv:
+            return (dx, None, None, None, None, None, None, dwr, dbr, None)
         return (dx, dwqkv[:C], dbqkv[:C], dwqkv[C:2 * C], dbqkv[C:2 * C], dwqkv[2 * C:],
                 dbqkv[2 * C:], dwr, dbr, None)
 
