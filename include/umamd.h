@@ -43,9 +43,15 @@ enum {
   UM_EPI_STATS = 1,          /* y = acc + bias, per-block BN partial sums      */
   UM_EPI_SIGMOID_SCALE = 2,  /* y(f32) = scale * sigmoid(acc + bias)           */
   UM_EPI_RESIDUAL = 3,       /* y = acc + bias + residual                      */
-  UM_EPI_STAT_SLOTS = 4      /* y = acc + bias, BN sums f64-atomically added into
+  UM_EPI_STAT_SLOTS = 4,     /* y = acc + bias, BN sums f64-atomically added into
                                 stats_partials viewed as double[UM_STAT_SLOTS][K][2]
                                 (zeroed by the caller; see um_bn_elu_fwd_slots)  */
+  UM_EPI_ELU = 5             /* y = elu(acc + bias), stored in ydtype (the
+                                activation dtype or f32): the inference form of
+                                Conv2d -> BatchNorm2d(eval) -> ELU with the BN
+                                folded into wf / bias (um_bn_fold).  um_conv2d_fwd
+                                only (not um_conv2d_fwd_up2); takes no statistics
+                                and never accumulates                            */
 };
 /* f64 slots of the atomic BN statistics (UM_EPI_STAT_SLOTS, *_slots entries) */
 #define UM_STAT_SLOTS 16
@@ -223,6 +229,20 @@ int um_bn_coeffs(const double* stats, double count, int C, const float* gamma,
                  const float* beta, float eps, float momentum, float* running_mean,
                  float* running_var, long long* num_batches_tracked, float* mean,
                  float* invstd, float* scale, float* shift, hipStream_t stream);
+/* Inference: fold an eval-mode nn.BatchNorm2d (running statistics) into the
+ * nn.Conv2d in front of it, so that Conv2d -> BatchNorm2d.eval() -> ELU
+ * (reference model/layers/encoder.py:41-44, model/layers/decoder.py:80-84)
+ * becomes one um_conv2d_fwd(UM_EPI_ELU).  Per output channel k, in f64:
+ *   s[k]         = gamma[k] / sqrt(running_var[k] + eps)
+ *   w_out[k,...] = w[k,...] * s[k]                      ([K][Creal][R][R], f32)
+ *   b_out[k]     = (bias[k] - running_mean[k]) * s[k] + beta[k]
+ * gamma / beta null: 1 / 0 (affine=False); bias null: 0; running_mean and
+ * running_var null: no BN (w_out = w, b_out = bias).  All buffers f32,
+ * caller-owned; w_out then goes through um_pack_weight_seg.  Build / refresh
+ * time only (one small launch per layer). */
+int um_bn_fold(const float* w, const float* bias, int K, int Creal, int R, const float* gamma,
+               const float* beta, const float* running_mean, const float* running_var,
+               float eps, float* w_out, float* b_out, hipStream_t stream);
 /* pool_parts (optional, SE squeeze of decoder.py:124-136 fused in): per-block
  * channel sums of a, [um_bn_fwd_pool_parts(M, HW)][C], HW = pixels per image */
 int um_bn_fwd_pool_parts(long M, long HW);

@@ -504,6 +504,49 @@ int um_bn_coeffs(const double* stats, double count, int C, const float* gamma, c
 }  // extern "C"
 
 namespace {
+// Eval-mode BN folded into the conv in front of it (um_bn_fold): thread i
+// scales weight element i of row k = i / crr by s[k] (f64, rounded once);
+// the first K threads also write the folded bias.
+__global__ void bn_fold_kernel(const float* __restrict__ w, const float* __restrict__ bias, int K,
+                               long crr, const float* __restrict__ gamma,
+                               const float* __restrict__ beta, const float* __restrict__ rmean,
+                               const float* __restrict__ rvar, float eps,
+                               float* __restrict__ w_out, float* __restrict__ b_out) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)K * crr) return;
+  auto s_of = [&](int k) -> double {
+    if (rvar == nullptr) return 1.0;
+    return (gamma ? (double)gamma[k] : 1.0) / sqrt((double)rvar[k] + (double)eps);
+  };
+  w_out[i] = (float)((double)w[i] * s_of((int)(i / crr)));
+  if (i < K) {
+    const int k = (int)i;
+    const double b = bias ? (double)bias[k] : 0.0;
+    const double m = rmean ? (double)rmean[k] : 0.0;
+    b_out[k] = (float)((b - m) * s_of(k) + (beta ? (double)beta[k] : 0.0));
+  }
+}
+}  // namespace
+
+extern "C" {
+
+int um_bn_fold(const float* w, const float* bias, int K, int Creal, int R, const float* gamma,
+               const float* beta, const float* running_mean, const float* running_var,
+               float eps, float* w_out, float* b_out, hipStream_t st) {
+  UM_CHECK_ARG(w != nullptr && w_out != nullptr && b_out != nullptr && K > 0 && Creal > 0 && R > 0,
+               "um_bn_fold: w / w_out / b_out and positive K, Creal, R");
+  UM_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr),
+               "um_bn_fold: running_mean and running_var come together");
+  const long crr = (long)Creal * R * R;
+  hipLaunchKernelGGL(bn_fold_kernel, dim3((unsigned)ceil_div((long)K * crr, 256l)), dim3(256), 0, st,
+                     w, bias, K, crr, gamma, beta, running_mean, running_var, eps, w_out, b_out);
+  UM_LAUNCH_CHECK();
+  return UM_OK;
+}
+
+}  // extern "C"
+
+namespace {
 // Channel-slice plan of the three BN passes: small layers (M * C up to 8M
 // elements) with C >= 128 take 64-channel slices (tuning key bn_slice = 0 turns
 // it off) and rows such that the grid has ~512 blocks (>= 32 rows: the 32

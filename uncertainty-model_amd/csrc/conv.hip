@@ -1220,6 +1220,8 @@ static int conv2d_fwd(int dtype, int N, int H, int W, int C, int ldx, const void
   UM_CHECK_ARG((epilogue != UM_EPI_STATS && epilogue != UM_EPI_STAT_SLOTS) || stats != nullptr,
                "um_conv2d_fwd: stats buffer missing");
   UM_CHECK_ARG(epilogue != UM_EPI_RESIDUAL || residual != nullptr, "um_conv2d_fwd: residual missing");
+  UM_CHECK_ARG(epilogue != UM_EPI_ELU || (!accumulate && stats == nullptr),
+               "um_conv2d_fwd: UM_EPI_ELU takes no statistics and does not accumulate");
   UM_CHECK_ARG(ydtype == dtype || ydtype == UM_F32, "um_conv2d_fwd: ydtype must be dtype or f32");
   umamd::IgArgs a{};
   a.a = x; a.ah = H; a.aw = W; a.ach = C; a.lda = ldx;

@@ -66,10 +66,16 @@ __device__ __forceinline__ int himg(int p, int c) { return p * CK + ((c ^ ((p >>
 // staged epilogue switch (tuning key halo_staged, read on the host into the
 // launch's argument block)
 #define umamd_halo_staged (a.staged)
+// WM + 4: the same weight mode with the UM_EPI_ELU epilogue (forward only).
+// A compile-time flag inside WM, so the existing instantiations keep their
+// names and code: as a runtime branch ELU cost every one of them 2 VGPRs (some
+// their AGPR granule), and a shared device-function body behind two kernel
+// templates moved 13 of them by 1-5 VGPRs (one lost a wave per SIMD).
 template <int R, int BN, bool FLIP, bool REFLECT, int WM>
 __global__ void __launch_bounds__(256) halo_conv_kernel(IgArgs a, int tiles_x, int tiles_y,
                                                         int ntiles) {
-  constexpr bool PF2 = WM == 1, RES = WM == 2;
+  constexpr bool ELU = WM >= 4;
+  constexpr bool PF2 = (WM & 3) == 1, RES = (WM & 3) == 2;
   constexpr int HH = TH + R - 1, HWd = TW + R - 1, HP = HH * HWd;
   constexpr int PIECES = HP * 4;                 // 16-byte pieces per chunk
   constexpr int NP = (PIECES + 255) / 256;       // per thread
@@ -371,6 +377,7 @@ __global__ void __launch_bounds__(256) halo_conv_kernel(IgArgs a, int tiles_x, i
           if (a.epilogue == UM_EPI_RESIDUAL)
             v += to_f32(reinterpret_cast<const bf16_t*>(a.residual)[m * a.ldr + n]);
           if (a.epilogue == UM_EPI_SIGMOID_SCALE) v = a.epi_scale * sigmoidf_(v);
+          if constexpr (ELU) v = eluf_(v);  // before the staging store
           if (staged) {
             sE[(((2 * wave + (i >> 1)) * TW + (i & 1) * 16 + rg + q) * JP + j % JP) * 16 + nc] =
                 from_f32<bf16_t>(v);
@@ -489,8 +496,11 @@ void launch_rp(const IgArgs& a, int ncb, int tiles_x, int tiles_y, size_t shm, h
     const dim3 grid(WM == 2 ? persist_grid(kernel, ntiles, ncb, shm) : ntiles, ncb);
     hipLaunchKernelGGL(kernel, grid, dim3(256), shm, st, a, tiles_x, tiles_y, ntiles);
   };
+  const bool reflect = a.pmode == umamd::IG_PAD_REFLECT;
   if (a.flip) go(halo_conv_kernel<R, BN, true, false, WM>);
-  else if (a.pmode == umamd::IG_PAD_REFLECT) go(halo_conv_kernel<R, BN, false, true, WM>);
+  else if (a.epilogue == UM_EPI_ELU && reflect) go(halo_conv_kernel<R, BN, false, true, WM + 4>);
+  else if (a.epilogue == UM_EPI_ELU) go(halo_conv_kernel<R, BN, false, false, WM + 4>);
+  else if (reflect) go(halo_conv_kernel<R, BN, false, true, WM>);
   else go(halo_conv_kernel<R, BN, false, false, WM>);
 }
 
@@ -546,6 +556,7 @@ namespace umamd {
 
 bool halo_applicable(int dtype, const IgArgs& a, int min_tiles, int max_nc) {
   if (dtype != UM_BF16 || a.stride != 1 || a.cls) return false;
+  if (a.epilogue == UM_EPI_ELU && a.flip) return false;  // a forward epilogue
   if (a.R != 3 && a.R != 5 && a.R != 7) return false;
   if (a.pmode == IG_FOLD) return false;                         // reflect transpose: igemm
   if (a.flip && a.pmode != IG_PAD_ZERO) return false;

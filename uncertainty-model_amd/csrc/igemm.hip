@@ -114,7 +114,8 @@ struct ARow {
 };
 
 // MODE: 0 plain rows, 1 parity class rows (stride-2 data gradient), 2 the
-// border list of the reflect fold (IgArgs::border)
+// border list of the reflect fold (IgArgs::border), 3 plain rows with the
+// UM_EPI_ELU epilogue (everything but igemm_epilogue treats it as 0)
 template <int MODE>
 __device__ __forceinline__ ARow decode_row(const IgArgs& a, int m) {
   constexpr bool CLS = MODE == 1;
@@ -266,6 +267,7 @@ __device__ __forceinline__ void igemm_epilogue(const IgArgs& a, float* __restric
         if (a.epilogue == UM_EPI_RESIDUAL)
           v += to_f32(reinterpret_cast<const T*>(a.residual)[(long)m * a.ldr + n]);
         if (a.epilogue == UM_EPI_SIGMOID_SCALE) v = a.epi_scale * sigmoidf_(v);
+        if constexpr (MODE == 3) v = eluf_(v);  // UM_EPI_ELU (see launch)
         if (a.out_f32) {
           float* o = reinterpret_cast<float*>(a.out) + off;
           if (a.accumulate) v += *o;
@@ -870,6 +872,7 @@ __device__ __forceinline__ void splitk_epi_rows(const IgArgs& a, const float* __
         if (a.epilogue == UM_EPI_RESIDUAL)
           v[e] += to_f32(reinterpret_cast<const T*>(a.residual)[m * a.ldr + n + e]);
         if (a.epilogue == UM_EPI_SIGMOID_SCALE) v[e] = a.epi_scale * sigmoidf_(v[e]);
+        if (a.epilogue == UM_EPI_ELU) v[e] = eluf_(v[e]);  // on the summed partials, once
       }
       // the row's output offset once (the border mode maps it through the
       // reflect list), then the 4 columns as one vector access when aligned
@@ -1147,6 +1150,9 @@ void split_plan(Plan& p, int M, int NC, int taps, int ach, long ws_bytes, bool g
 template <typename T, int BK, int BM, int BN, int WM, int WN, int MODE>
 int launch_cls(const IgArgs& a, const Plan& p, float* ws, hipStream_t st) {
   const int ntm = ceil_div(a.M, BM), ntn = ceil_div(a.NC, BN);
+  // split launches write raw partials: the ELU mode shares the plain kernels
+  // there, and splitk_epilogue_kernel applies ELU to the sum (runtime branch)
+  constexpr int SM = MODE == 3 ? 0 : MODE;
   if constexpr (sizeof(T) == 2 && BK == 64 && WM == 2 && WN == 2 && MODE != 2) {
     if (a.pmode != umamd::IG_FOLD && (knobs().glds & (BM == 64 ? 1 : 2))) {
       const bool w8 = BM == 64 && (knobs().glds & 4);
@@ -1156,26 +1162,26 @@ int launch_cls(const IgArgs& a, const Plan& p, float* ws, hipStream_t st) {
       const IgArgs& g = a;
       const dim3 grid(ntm * ntn, 1, p.splits);
       if (deep && p.splits > 1)
-        hipLaunchKernelGGL((igemm_glds_kernel<BM, BN, 8, true, MODE, DEEP>), grid, dim3(512), 0, st, g,
+        hipLaunchKernelGGL((igemm_glds_kernel<BM, BN, 8, true, SM, DEEP>), grid, dim3(512), 0, st, g,
                            ws, p.steps, p.per, ntn);
       else if (deep)
         hipLaunchKernelGGL((igemm_glds_kernel<BM, BN, 8, false, MODE, DEEP>), grid, dim3(512), 0, st, g,
                            ws, p.steps, p.per, ntn);
       else if (w8 && p.splits > 1)
-        hipLaunchKernelGGL((igemm_glds_kernel<BM, BN, 8, true, MODE, 3>), grid, dim3(512), 0, st, g, ws,
+        hipLaunchKernelGGL((igemm_glds_kernel<BM, BN, 8, true, SM, 3>), grid, dim3(512), 0, st, g, ws,
                            p.steps, p.per, ntn);
       else if (w8)
         hipLaunchKernelGGL((igemm_glds_kernel<BM, BN, 8, false, MODE, 3>), grid, dim3(512), 0, st, g, ws,
                            p.steps, p.per, ntn);
       else if (p.splits > 1)
-        hipLaunchKernelGGL((igemm_glds_kernel<BM, BN, 4, true, MODE, 3>), grid, dim3(256), 0, st, g, ws,
+        hipLaunchKernelGGL((igemm_glds_kernel<BM, BN, 4, true, SM, 3>), grid, dim3(256), 0, st, g, ws,
                            p.steps, p.per, ntn);
       else
         hipLaunchKernelGGL((igemm_glds_kernel<BM, BN, 4, false, MODE, 3>), grid, dim3(256), 0, st, g, ws,
                            p.steps, p.per, ntn);
       if (p.splits > 1) {
         const int er = a.epilogue == UM_EPI_STATS ? a.stats_rows : EPI_ROWS;
-        hipLaunchKernelGGL((splitk_epilogue_kernel<T, MODE>),
+        hipLaunchKernelGGL((splitk_epilogue_kernel<T, SM>),
                            dim3(ceil_div(a.M, er), ceil_div(a.NC, EPI_COLS)), dim3(256), 0, st, a,
                            (const float*)ws, p.splits, er);
       }
@@ -1184,10 +1190,10 @@ int launch_cls(const IgArgs& a, const Plan& p, float* ws, hipStream_t st) {
     }
   }
   if (p.splits > 1) {
-    hipLaunchKernelGGL((igemm_kernel<T, BK, BM, BN, WM, WN, true, MODE>),
+    hipLaunchKernelGGL((igemm_kernel<T, BK, BM, BN, WM, WN, true, SM>),
                        dim3(ntm * ntn, 1, p.splits), dim3(256), 0, st, a, ws, p.steps, p.per, ntn);
     const int er = a.epilogue == UM_EPI_STATS ? a.stats_rows : EPI_ROWS;
-    hipLaunchKernelGGL((splitk_epilogue_kernel<T, MODE>),
+    hipLaunchKernelGGL((splitk_epilogue_kernel<T, SM>),
                        dim3(ceil_div(a.M, er), ceil_div(a.NC, EPI_COLS)), dim3(256), 0, st, a,
                        (const float*)ws, p.splits, er);
   } else {
@@ -1200,8 +1206,11 @@ int launch_cls(const IgArgs& a, const Plan& p, float* ws, hipStream_t st) {
 
 template <typename T, int BK, int BM, int BN, int WM, int WN>
 int launch(const IgArgs& a, const Plan& p, float* ws, hipStream_t st) {
-  return a.cls ? launch_cls<T, BK, BM, BN, WM, WN, 1>(a, p, ws, st)
-               : launch_cls<T, BK, BM, BN, WM, WN, 0>(a, p, ws, st);
+  if (a.cls) return launch_cls<T, BK, BM, BN, WM, WN, 1>(a, p, ws, st);
+  // UM_EPI_ELU as a compile-time mode: a runtime branch in the shared
+  // epilogue cost up to 31 VGPRs in instantiations that never take it
+  if (a.epilogue == UM_EPI_ELU) return launch_cls<T, BK, BM, BN, WM, WN, 3>(a, p, ws, st);
+  return launch_cls<T, BK, BM, BN, WM, WN, 0>(a, p, ws, st);
 }
 
 template <typename T>

@@ -51,8 +51,11 @@ __device__ __forceinline__ void add4(const bf16_t* p, float* v) {
   v[3] += __uint_as_float(u.y & 0xffff0000u);
 }
 
-template <int KS, bool F32, bool STATS>
-__global__ void __launch_bounds__(256) stream1x1_kernel(IgArgs a, int nb, long nstrips) {
+// ELU: the UM_EPI_ELU epilogue, compiled into kernels of its own
+// (stream1x1_elu_kernel; as a runtime branch it cost the existing ones 2-5
+// VGPRs, two of them a wave per SIMD)
+template <int KS, bool F32, bool STATS, bool ELU>
+__device__ __forceinline__ void stream1x1_body(const IgArgs& a, int nb, long nstrips) {
   extern __shared__ __attribute__((aligned(16))) bf16_t sW[];  // KS x nr x 32
   __shared__ float sStat[STATS ? 4 : 1][STATS ? S1STATNB * 16 : 1][2];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -124,6 +127,10 @@ __global__ void __launch_bounds__(256) stream1x1_kernel(IgArgs a, int nb, long n
           }
           if (a.epilogue == UM_EPI_RESIDUAL)
             add4(reinterpret_cast<const bf16_t*>(a.residual) + m * a.ldr + n, v);
+          if constexpr (ELU) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = eluf_(v[j]);
+          }
           if constexpr (F32) {
             float* o = reinterpret_cast<float*>(a.out) + m * a.ld_out + n;
             if (a.accumulate) {
@@ -193,8 +200,17 @@ __global__ void __launch_bounds__(256) stream1x1_kernel(IgArgs a, int nb, long n
 // runs the KS x NG MFMAs (D = W . A^T as stream1x1_kernel: each lane ends with
 // 4 consecutive output channels of one pixel) and the same epilogues (bias,
 // residual, f32 output, accumulate, BN statistics into f64 slots).
-template <int KS, int NG, bool F32, bool STATS>
-__global__ void __launch_bounds__(256) s1x1_small_kernel(IgArgs a, long nstrips) {
+template <int KS, bool F32, bool STATS>
+__global__ void __launch_bounds__(256) stream1x1_kernel(IgArgs a, int nb, long nstrips) {
+  stream1x1_body<KS, F32, STATS, false>(a, nb, nstrips);
+}
+template <int KS, bool F32>
+__global__ void __launch_bounds__(256) stream1x1_elu_kernel(IgArgs a, int nb, long nstrips) {
+  stream1x1_body<KS, F32, false, true>(a, nb, nstrips);
+}
+
+template <int KS, int NG, bool F32, bool STATS, bool ELU>
+__device__ __forceinline__ void s1x1_small_body(const IgArgs& a, long nstrips) {
   extern __shared__ __attribute__((aligned(16))) bf16_t sW[];  // KS x (NG*16) x 32
   __shared__ float sStat[STATS ? 4 : 1][STATS ? NG * 16 : 1][2];
   constexpr int NR = NG * 16;
@@ -248,6 +264,10 @@ __global__ void __launch_bounds__(256) s1x1_small_kernel(IgArgs a, long nstrips)
       }
       if (a.epilogue == UM_EPI_RESIDUAL)
         add4(reinterpret_cast<const bf16_t*>(a.residual) + m * a.ldr + n, v);
+      if constexpr (ELU) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = eluf_(v[j]);
+      }
       if constexpr (F32) {
         float* o = reinterpret_cast<float*>(a.out) + m * a.ld_out + n;
         if (a.accumulate) {
@@ -298,6 +318,15 @@ __global__ void __launch_bounds__(256) s1x1_small_kernel(IgArgs a, long nstrips)
   }
 }
 
+template <int KS, int NG, bool F32, bool STATS>
+__global__ void __launch_bounds__(256) s1x1_small_kernel(IgArgs a, long nstrips) {
+  s1x1_small_body<KS, NG, F32, STATS, false>(a, nstrips);
+}
+template <int KS, int NG, bool F32>
+__global__ void __launch_bounds__(256) s1x1_small_elu_kernel(IgArgs a, long nstrips) {
+  s1x1_small_body<KS, NG, F32, false, true>(a, nstrips);
+}
+
 }  // namespace
 
 namespace umamd {
@@ -319,7 +348,7 @@ bool stream1x1_applicable(int dtype, const IgArgs& a) {
   if (!al(a.a, 16) || !al(a.b, 16) || !al(a.out, a.out_f32 ? 16 : 8) ||
       (a.residual != nullptr && !al(a.residual, 8)))
     return false;
-  if (a.epilogue == UM_EPI_NONE) return true;
+  if (a.epilogue == UM_EPI_NONE || a.epilogue == UM_EPI_ELU) return true;
   if (a.epilogue == UM_EPI_RESIDUAL) return !a.out_f32 && a.ldr % 4 == 0 && a.residual != nullptr;
   if (a.epilogue == UM_EPI_STATS)
     return a.stat_slots && a.out_f32 && a.NC <= 16 * S1STATNB && a.stats != nullptr;
@@ -349,7 +378,7 @@ bool s1x1_small_applicable(int dtype, const IgArgs& a) {
   if (!al(a.a, 16) || !al(a.b, 16) || !al(a.out, a.out_f32 ? 16 : 8) ||
       (a.residual != nullptr && !al(a.residual, 8)))
     return false;
-  if (a.epilogue == UM_EPI_NONE) return true;
+  if (a.epilogue == UM_EPI_NONE || a.epilogue == UM_EPI_ELU) return true;
   if (a.epilogue == UM_EPI_RESIDUAL) return !a.out_f32 && a.ldr % 4 == 0 && a.residual != nullptr;
   if (a.epilogue == UM_EPI_STATS) return a.stat_slots && a.out_f32 && a.stats != nullptr;
   return false;
@@ -368,28 +397,28 @@ int s1x1_small_run(const IgArgs& a, hipStream_t st) {
   const long gx = std::max<long>(1, std::min<long>(ceil_div(nstrips, 4), std::max<long>(1, 1024 / gy)));
   const size_t lds = (size_t)ks * ng * 16 * 32 * sizeof(bf16_t);
   const bool stats = a.epilogue == UM_EPI_STATS;
-#define UM_S1S(KS_, NG_, F32_, ST_)                                                               \
-  hipLaunchKernelGGL((s1x1_small_kernel<KS_, NG_, F32_, ST_>), dim3((int)gx, gy), dim3(256), lds, st, \
-                     a, nstrips)
-#define UM_S1SK(NG_, F32_, ST_)                    \
-  switch (ks) {                                    \
-    case 1: UM_S1S(1, NG_, F32_, ST_); break;      \
-    case 2: UM_S1S(2, NG_, F32_, ST_); break;      \
-    case 4: UM_S1S(4, NG_, F32_, ST_); break;      \
-    case 8: UM_S1S(8, NG_, F32_, ST_); break;      \
-    default: UM_S1S(16, NG_, F32_, ST_); break;    \
+  const bool elu = a.epilogue == UM_EPI_ELU;
+#define UM_S1S(K_)                                                                   \
+  hipLaunchKernelGGL((K_), dim3((int)gx, gy), dim3(256), lds, st, a, nstrips)
+#define UM_S1SK(NAME_, ...)                                     \
+  switch (ks) {                                                 \
+    case 1: UM_S1S((NAME_<1, __VA_ARGS__>)); break;             \
+    case 2: UM_S1S((NAME_<2, __VA_ARGS__>)); break;             \
+    case 4: UM_S1S((NAME_<4, __VA_ARGS__>)); break;             \
+    case 8: UM_S1S((NAME_<8, __VA_ARGS__>)); break;             \
+    default: UM_S1S((NAME_<16, __VA_ARGS__>)); break;           \
   }
-#define UM_S1SN(F32_, ST_)              \
-  if (ng == 4) { UM_S1SK(4, F32_, ST_) } \
-  else { UM_S1SK(2, F32_, ST_) }
   if (stats) {
-    UM_S1SN(true, true)
+    if (ng == 4) { UM_S1SK(s1x1_small_kernel, 4, true, true) } else { UM_S1SK(s1x1_small_kernel, 2, true, true) }
+  } else if (elu && a.out_f32) {
+    if (ng == 4) { UM_S1SK(s1x1_small_elu_kernel, 4, true) } else { UM_S1SK(s1x1_small_elu_kernel, 2, true) }
+  } else if (elu) {
+    if (ng == 4) { UM_S1SK(s1x1_small_elu_kernel, 4, false) } else { UM_S1SK(s1x1_small_elu_kernel, 2, false) }
   } else if (a.out_f32) {
-    UM_S1SN(true, false)
+    if (ng == 4) { UM_S1SK(s1x1_small_kernel, 4, true, false) } else { UM_S1SK(s1x1_small_kernel, 2, true, false) }
   } else {
-    UM_S1SN(false, false)
+    if (ng == 4) { UM_S1SK(s1x1_small_kernel, 4, false, false) } else { UM_S1SK(s1x1_small_kernel, 2, false, false) }
   }
-#undef UM_S1SN
 #undef UM_S1SK
 #undef UM_S1S
   UM_LAUNCH_CHECK();
@@ -403,22 +432,25 @@ int stream1x1_run(const IgArgs& a, hipStream_t st) {
   const int grid = (int)std::min<long>(want, 2048);
   const size_t lds = (size_t)ks * nb * 16 * 32 * sizeof(bf16_t);
   const bool stats = a.epilogue == UM_EPI_STATS;
-#define UM_S1(KS_, F32_, ST_)                                                               \
-  hipLaunchKernelGGL((stream1x1_kernel<KS_, F32_, ST_>), dim3(grid), dim3(256), lds, st, a, nb, \
-                     nstrips)
-#define UM_S1K(F32_, ST_)                     \
-  switch (ks) {                               \
-    case 1: UM_S1(1, F32_, ST_); break;       \
-    case 2: UM_S1(2, F32_, ST_); break;       \
-    case 4: UM_S1(4, F32_, ST_); break;       \
-    default: UM_S1(8, F32_, ST_); break;      \
+  const bool elu = a.epilogue == UM_EPI_ELU;
+#define UM_S1(K_) hipLaunchKernelGGL((K_), dim3(grid), dim3(256), lds, st, a, nb, nstrips)
+#define UM_S1K(NAME_, ...)                                   \
+  switch (ks) {                                              \
+    case 1: UM_S1((NAME_<1, __VA_ARGS__>)); break;           \
+    case 2: UM_S1((NAME_<2, __VA_ARGS__>)); break;           \
+    case 4: UM_S1((NAME_<4, __VA_ARGS__>)); break;           \
+    default: UM_S1((NAME_<8, __VA_ARGS__>)); break;          \
   }
   if (stats) {
-    UM_S1K(true, true)
+    UM_S1K(stream1x1_kernel, true, true)
+  } else if (elu && a.out_f32) {
+    UM_S1K(stream1x1_elu_kernel, true)
+  } else if (elu) {
+    UM_S1K(stream1x1_elu_kernel, false)
   } else if (a.out_f32) {
-    UM_S1K(true, false)
+    UM_S1K(stream1x1_kernel, true, false)
   } else {
-    UM_S1K(false, false)
+    UM_S1K(stream1x1_kernel, false, false)
   }
 #undef UM_S1K
 #undef UM_S1

@@ -20,6 +20,7 @@ UM_F32, UM_BF16 = 0, 1
 Y_ACT = 0x100
 PAD_ZERO, PAD_REFLECT = 0, 1
 EPI_NONE, EPI_STATS, EPI_SIGMOID_SCALE, EPI_RESIDUAL, EPI_STAT_SLOTS = 0, 1, 2, 3, 4
+EPI_ELU = 5  # UM_EPI_ELU: y = elu(acc + bias), the folded conv+BN(eval)+ELU of umamd.infer
 STAT_SLOTS = 16  # UM_STAT_SLOTS (include/umamd.h)
 CAT_COPY, CAT_UP2, CAT_PSHUF = 0, 1, 2
 LABEL_MSE, LABEL_BCE = 0, 1  # UM_LABEL_* (include/umamd.h)
@@ -87,6 +88,7 @@ _SIG = {
                                 's']),
     'um_bn_bwd_stats_coeffs': (_I, [_P, _I, _I, _P, _D, _P, _P, _P, _P, _P, _P, _P, _P, 's']),
     'um_bn_coeffs': (_I, [_P, _D, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _P, 's']),
+    'um_bn_fold': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _F, _P, _P, 's']),
     'um_bn_fwd_pool_parts': (_I, [_L, _L]),
     'um_bn_fwd_pool_parts_c': (_I, [_L, _L, _I]),
     'um_bn_elu_fwd': (_I, [_I, _L, _I, _P, _I, _P, _P, _P, _I, _I, _L, _P, 's']),

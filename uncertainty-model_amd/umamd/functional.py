@@ -584,6 +584,23 @@ class ConvSpec:
         self.elu = elu
 
 
+# the inference engine whose forward is running (umamd.infer.InferenceEngine):
+# _cbe_fwd consults it for layers whose BN is in eval mode (or absent)
+_INFER = None
+
+
+@contextmanager
+def infer_scope(engine):
+    """Make ``engine`` the inference engine of the convs called inside."""
+    global _INFER
+    prev = _INFER
+    _INFER = engine
+    try:
+        yield
+    finally:
+        _INFER = prev
+
+
 class _CBEState:
     """What a conv+BN+ELU forward keeps for its backward (the autograd ctx
     of ConvBNELUFn, or one node of a GraphBlockFn)."""
@@ -605,7 +622,22 @@ def _cbe_fwd(x, weight, bias, gamma, beta, w1, w2, spec: ConvSpec, merge=None, y
     K, Creal, R, _ = weight.shape
     bn = spec.bn
     dev = x.device
-    wf, wT = _pack(weight, Cp, x.dtype, segs=spec.segs) if yconv is None else (None, None)
+    # frozen weights and statistics (umamd.infer): BN folded into the conv, or
+    # at least its coefficients taken from the engine instead of rebuilt
+    inf = _INFER if (bn is None or not bn.training) else None
+    if inf is not None and inf.fused and w1 is None and yconv is None and spec.elu:
+        a = inf.conv_elu(x, weight, bias, spec)
+        ctx.merged = None
+        if merge is not None:
+            msrcs, mwidx, mw = merge
+            ctx.merged = _merge_launch([a if t is None else t for t in msrcs], mw, mwidx, None,
+                                       torch.empty_like(a))
+        ctx.spec, ctx.sync, ctx.slots_b, ctx.has_bn, ctx.se = spec, None, None, False, None
+        ctx.geom = None
+        ctx.saved = (None,) * 10  # forward only: nothing to differentiate
+        return (a,), ctx
+    wf, wT = _pack(weight, Cp, x.dtype, wT=inf is None, segs=spec.segs) if yconv is None \
+        else (None, None)
     P = (H + 2 * spec.pad - R) // spec.stride + 1
     Q = (W + 2 * spec.pad - R) // spec.stride + 1
     M = N * P * Q
@@ -642,8 +674,8 @@ def _cbe_fwd(x, weight, bias, gamma, beta, w1, w2, spec: ConvSpec, merge=None, y
         y = _conv_fwd(x, wf, bias_f, K, R, spec.stride, spec.pad, spec.pad_mode,
                       out_dtype=_ydtype(x.dtype), epi=epi, stats=parts, creal=Creal) \
             if yconv is None else yconv(epi, parts, bias_f)
-        mean, invstd, scale, shift = _bn_forward_coeffs(parts, nparts, K, M, bn, sync,
-                                                        training, dev)
+        mean, invstd, scale, shift = inf.coeffs(bn) if inf is not None else \
+            _bn_forward_coeffs(parts, nparts, K, M, bn, sync, training, dev)
     else:  # ConvELUBlock(batch_norm=False): identity normalisation
         sync = None
         training = False
