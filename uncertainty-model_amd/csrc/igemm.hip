@@ -616,22 +616,6 @@ __device__ __forceinline__ void wait_later(int later) {
   }
 }
 
-template <int MODE>
-__device__ __forceinline__ const bf16_t* gather_ptr(const IgArgs& a, const bf16_t* src,
-                                                     const ARow& w, int r, int s, int c) {
-  constexpr bool CLS = MODE == 1;
-  const bf16_t* zero = reinterpret_cast<const bf16_t*>(g_zero_page);
-  if (!w.ok || c >= a.ach) return zero;
-  int yy = CLS ? w.y0 - r : w.y0 + r, xx = CLS ? w.x0 - s : w.x0 + s;
-  if (a.pmode == umamd::IG_PAD_REFLECT) {
-    yy = reflect_idx(yy, a.ah);
-    xx = reflect_idx(xx, a.aw);
-  } else if (yy < 0 || yy >= a.ah || xx < 0 || xx >= a.aw) {
-    return zero;
-  }
-  return src + w.base + ((long)yy * a.aw + xx) * a.lda + c;
-}
-
 // NW = 4 or 8 waves; with 8, a 64x64 tile gives each wave a 16x32 sub-tile
 // and every SIMD two waves of the block to overlap the per-step latencies.
 // NST stages: 3 (48 KB for 64x64, several blocks per CU) or deeper for grids
@@ -682,63 +666,109 @@ __device__ __forceinline__ void glds_tile(const IgArgs& a, float* __restrict__ w
   const bf16_t* __restrict__ bsrc = reinterpret_cast<const bf16_t*>(a.b);
   const bf16_t* zero = reinterpret_cast<const bf16_t*>(g_zero_page);
 
-  // this lane's rows: A rows wave*(BM/4) + 8i + (lane >> 3), B likewise
+  // this lane's rows: A rows wave*(BM/4) + 8i + (lane >> 3), B likewise.
+  // Per row only what a tap change needs: the image's base pointer at the
+  // lane's channel chunk and the coordinates of tap (0,0).
   const int lr = lane >> 3, lp = lane & 7;
-  ARow arow[A_INS];
-  int ac8[A_INS];
+  const bf16_t* abase[A_INS];
+  int ay0[A_INS], ax0[A_INS];
+  bool aok[A_INS];
 #pragma unroll
   for (int i = 0; i < A_INS; ++i) {
     const int row = wave * (BM / NW) + i * 8 + lr;
-    ac8[i] = lp ^ (row & 7);
-    arow[i] = decode_row<MODE>(a, bm + row);
+    const ARow w = decode_row<MODE>(a, bm + row);
+    abase[i] = asrc + w.base + (lp ^ (row & 7)) * 8;
+    ay0[i] = w.y0;
+    ax0[i] = w.x0;
+    aok[i] = w.ok;
   }
-  int bc8[B_INS];
-  long boff_row[B_INS];
+  const bf16_t* bbase[B_INS];
   bool bok[B_INS];
 #pragma unroll
   for (int i = 0; i < B_INS; ++i) {
     const int row = wave * (BN / NW) + i * 8 + lr;
-    bc8[i] = lp ^ (row & 7);
     bok[i] = bn + row < a.NC;
-    boff_row[i] = (long)(bn + row) * a.ldb;
+    bbase[i] = bsrc + (long)(bn + row) * a.ldb + (lp ^ (row & 7)) * 8;
   }
 
   const int s_begin = SPLIT ? blockIdx.z * steps_per_split : 0;
   const int s_end = SPLIT ? min(steps, s_begin + steps_per_split) : steps;
   const int nsteps = s_end - s_begin;
-  const int nchunk = (a.ach + BK - 1) / BK;
-  int tap = s_begin / nchunk;
-  int c0 = (s_begin - tap * nchunk) * BK;
+  // ach % 64 == 0 on this path (make_plan, cls4_glds_ok): a tap is nchunk
+  // whole k-steps, so no lane's chunk ever lies past ach
+  const int nchunk = a.ach / BK;
+  const int tap0 = s_begin / nchunk;
   const int RX = CLS ? a.Rx : a.R;
-  int r = tap / RX, s = tap - (tap / RX) * RX;
+  int r = tap0 / RX, s = tap0 - (tap0 / RX) * RX;
 
-  // issue the k-step at the cursor (r, s, c0) into stage `st`, then advance
-  auto issue = [&](int st) {
-    bf16_t* base = smem + st * STAGE;
+  // Tap state: the address work of a k-step (bounds or reflect, the 64-bit
+  // pixel offset, the zero-page select, the weight tap offset) depends on the
+  // tap alone, so it runs once per tap.  Within a tap the pointers advance
+  // by one 64-channel chunk per k-step; zero-page rows advance by 0.
+  const bf16_t* ap[A_INS];
+  const bf16_t* bp[B_INS];
+  int ainc[A_INS], binc[B_INS];
+#pragma unroll
+  for (int i = 0; i < B_INS; ++i) binc[i] = bok[i] ? BK : 0;
+  auto next_tap = [&]() {
 #pragma unroll
     for (int i = 0; i < A_INS; ++i) {
-      const bf16_t* g = gather_ptr<MODE>(a, asrc, arow[i], r, s, c0 + ac8[i] * 8);
-      __builtin_amdgcn_global_load_lds(
-          g, (__attribute__((address_space(3))) void*)(base + (wave * (BM / NW) + i * 8) * BK), 16,
-          0, 0);
+      int yy = CLS ? ay0[i] - r : ay0[i] + r, xx = CLS ? ax0[i] - s : ax0[i] + s;
+      bool in = aok[i];
+      if (a.pmode == umamd::IG_PAD_REFLECT) {
+        yy = reflect_idx(yy, a.ah);
+        xx = reflect_idx(xx, a.aw);
+      } else {
+        in = in && yy >= 0 && yy < a.ah && xx >= 0 && xx < a.aw;
+      }
+      ap[i] = in ? abase[i] + ((long)yy * a.aw + xx) * a.lda : zero;
+      ainc[i] = in ? BK : 0;
     }
     const int btap = CLS ? (a.r0y + 2 * r) * a.wR + (a.r0x + 2 * s)
                          : (a.flip ? (a.R - 1 - r) * a.R + (a.R - 1 - s) : r * a.R + s);
     const long boff = (long)btap * a.ach;
 #pragma unroll
+    for (int i = 0; i < B_INS; ++i) bp[i] = bok[i] ? bbase[i] + boff : zero;
+    if (++s == RX) { s = 0; ++r; }
+  };
+  // k-steps left in the cursor's tap; a split may begin inside one
+  next_tap();
+  int left = nchunk - (s_begin - tap0 * nchunk);
+  {
+    const int skip = nchunk - left;
+#pragma unroll
+    for (int i = 0; i < A_INS; ++i) ap[i] += skip * ainc[i];
+#pragma unroll
+    for (int i = 0; i < B_INS; ++i) bp[i] += skip * binc[i];
+  }
+
+  // issue the k-step at the cursor into stage `st`, then advance the cursor
+  auto issue = [&](int st) {
+    bf16_t* base = smem + st * STAGE;
+    if (left == 0) {
+      next_tap();
+      left = nchunk;
+    }
+    --left;
+    // (the address goes through a local: the host pass rejects a captured
+    // array element as the builtin's pointer argument)
+#pragma unroll
+    for (int i = 0; i < A_INS; ++i) {
+      const bf16_t* g = ap[i];
+      __builtin_amdgcn_global_load_lds(
+          g, (__attribute__((address_space(3))) void*)(base + (wave * (BM / NW) + i * 8) * BK),
+          16, 0, 0);
+      ap[i] += ainc[i];
+    }
+#pragma unroll
     for (int i = 0; i < B_INS; ++i) {
-      const int c = c0 + bc8[i] * 8;
-      const bf16_t* g = (bok[i] && c < a.ach) ? bsrc + boff_row[i] + boff + c : zero;
+      const bf16_t* g = bp[i];
       __builtin_amdgcn_global_load_lds(
           g,
           (__attribute__((address_space(3))) void*)(base + BM * BK +
                                                     (wave * (BN / NW) + i * 8) * BK),
           16, 0, 0);
-    }
-    c0 += BK;
-    if (c0 >= a.ach) {
-      c0 = 0;
-      if (++s == RX) { s = 0; ++r; }
+      bp[i] += binc[i];
     }
   };
 
@@ -751,12 +781,9 @@ __device__ __forceinline__ void glds_tile(const IgArgs& a, float* __restrict__ w
   const int frow = lane & 15, fg = lane >> 4;
   const int npro = nsteps < NST ? nsteps : NST;
   for (int p = 0; p < npro; ++p) issue(p);
-  for (int k = 0; k < nsteps; ++k) {
-    // this wave's loads of step k have landed when at most the later issued
-    // steps' loads are outstanding
-    wait_later<PER, NST - 1>(nsteps - 1 - k);
-    __builtin_amdgcn_s_barrier();  // every wave's DMA for step k is in LDS
-    const int cur = k % NST;
+  // the MFMAs of the k-step staged in `cur`, between its two barriers
+  auto compute = [&](int cur) {
+    __builtin_amdgcn_s_barrier();  // every wave's DMA for this step is in LDS
     const bf16_t* sA = smem + cur * STAGE;
     const bf16_t* sB = sA + BM * BK;
 #pragma unroll
@@ -775,7 +802,23 @@ __device__ __forceinline__ void glds_tile(const IgArgs& a, float* __restrict__ w
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // stage `cur` is free again
-    if (k + NST < nsteps) issue(cur);
+  };
+  // Steady state: NST k-steps are issued, so this wave's loads of step k have
+  // landed once at most the NST-1 later steps' are outstanding -- a constant
+  // count -- and the freed stage takes step k + NST.
+  int k = 0, cur = 0;
+  for (; k + NST < nsteps; ++k) {
+    wait_vm<(NST - 1) * PER>();
+    compute(cur);
+    issue(cur);
+    cur = cur + 1 == NST ? 0 : cur + 1;
+  }
+  // the last NST steps (or all of a shorter loop) only drain: at most
+  // min(later steps, NST-1) steps' loads may stay outstanding
+  for (; k < nsteps; ++k) {
+    wait_later<PER, NST - 1>(nsteps - 1 - k);
+    compute(cur);
+    cur = cur + 1 == NST ? 0 : cur + 1;
   }
   // all DMA retired (the last iteration waited vmcnt(0)); reuse LDS for stats
   __syncthreads();

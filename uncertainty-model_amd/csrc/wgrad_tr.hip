@@ -10,8 +10,10 @@
 // lane) come out of ds_read_b64_tr_b16 pairs.  The images swizzle 32-byte
 // channel chunks by pixel-row bits (the parity masks found conflict-free for
 // 8- and 4-chunk rows), double-buffered, one barrier per k-step, the next
-// step's global loads in flight during the MFMAs.  Pixel coordinates advance
-// incrementally (no division in the loop).  Split over pixels into f32 slabs
+// step's global loads in flight during the MFMAs.  Operand addresses advance
+// incrementally: DY pointers by a constant, X by its pixel (p, q) with 32-bit
+// row and column offsets inside the image (no division, no 64-bit multiply
+// in the loop).  Split over pixels into f32 slabs
 // [split][K][R*R*C] as the other weight-gradient kernels; wgrad_reduce_kernel
 // sums them.  Used for the bf16 convs the halo kernel does not cover (deep
 // layers with many channels or small maps).
@@ -35,6 +37,7 @@ struct TrArgs {
   float* slabs;
   int N, H, W, C, ldx, K, R, stride, pad, reflect, P, Q, ldy;
   int M, RRC, m_per_split;
+  int row_step;  // TBK / Q when a k-step is that many whole output rows, else 0
 };
 
 __device__ __forceinline__ int bit(int v, int b) { return (v >> b) & 1; }
@@ -55,7 +58,7 @@ __device__ __forceinline__ bf16x4_t tr_read(const bf16_t* p) {
       (__attribute__((address_space(3))) bf16x4_t*)(p));
 }
 
-// pixel coordinates advanced by a fixed step without division
+// pixel coordinates of GEMM row m (rows past mend decode as row 0 and are never loaded)
 struct Pix {
   int n, p, q;
   bool ok;
@@ -71,15 +74,6 @@ __device__ __forceinline__ Pix pix_at(long m, int P, int Q, long mend) {
   x.q = r - x.p * Q;
   return x;
 }
-__device__ __forceinline__ void pix_adv(Pix& x, int step, int P, int Q, long m, long mend) {
-  x.q += step;
-  while (x.q >= Q) {
-    x.q -= Q;
-    if (++x.p == P) { x.p = 0; ++x.n; }
-  }
-  x.ok = m < mend;
-}
-
 // TBK pixels per k-step (a multiple of the MFMA's 32): the loads of step
 // s+1 are in flight during the MFMAs of step s, so a larger step hides more
 // of the global-load latency per barrier (these GEMMs are latency-bound at
@@ -103,34 +97,60 @@ __global__ void __launch_bounds__(256) wgrad_tr_kernel(TrArgs a) {
   const long m_begin = (long)blockIdx.z * a.m_per_split;
   const long m_end = min((long)a.M, m_begin + a.m_per_split);
 
-  // staging assignments: A chunk u -> (row, c8), B likewise
-  int arow[A_PER], ac8[A_PER];
-  bool aok[A_PER];
-  Pix apx[A_PER];
+  // Staging assignments: A chunk u -> (row, c8), B likewise.  The load cursor
+  // is `mrel` pixels past m_begin; chunk u holds pixel mrel + row, valid while
+  // mrel < lim[u] (0 for chunks past K / RRC, which stay zero).
+  const int mlen = (int)(m_end - m_begin);
+  int mrel = 0;
+  // DY is pixel-major, so its chunk pointers just advance by TBK rows
+  const bf16_t* adp[A_PER];
+  int aso[A_PER], alim[A_PER];
+  const long astep = (long)TBK * a.ldy;
 #pragma unroll
   for (int u = 0; u < A_PER; ++u) {
     const int id = tid + u * 256;
-    arow[u] = id / (BM / 8);
-    ac8[u] = id % (BM / 8);
-    aok[u] = bk + ac8[u] * 8 < a.K;
-    apx[u] = pix_at(m_begin + arow[u], a.P, a.Q, m_end);
+    const int row = id / (BM / 8), c8 = id % (BM / 8);
+    aso[u] = img_off<NCA>(row, c8);
+    alim[u] = bk + c8 * 8 < a.K ? mlen - row : 0;
+    adp[u] = a.dy + (m_begin + row) * a.ldy + bk + c8 * 8;
   }
-  int brow[B_PER], bc8[B_PER], bry[B_PER], brx[B_PER], bch[B_PER];
-  bool bok[B_PER];
-  Pix bpx[B_PER];
+  // X: per chunk the image pointer at the chunk's channel, the pixel (p, q),
+  // the tap's source coordinates of pixel (0, 0), and the element offsets of
+  // the source row and column (-1: zero padding), redone when p or q moves
+  const bf16_t* bimg[B_PER];
+  int bso[B_PER], blim[B_PER], bp[B_PER], bq[B_PER], by0[B_PER], bx0[B_PER], byo[B_PER],
+      bxo[B_PER];
+  const long img_stride = (long)a.H * a.W * a.ldx;
+  const int row_pitch = a.W * a.ldx;
+  auto yoff = [&](int p, int y0) {
+    int yy = p * a.stride + y0;
+    if (a.reflect) yy = reflect_idx(yy, a.H);
+    return (yy < 0 || yy >= a.H) ? -1 : yy * row_pitch;
+  };
+  auto xoff = [&](int q, int x0) {
+    int xx = q * a.stride + x0;
+    if (a.reflect) xx = reflect_idx(xx, a.W);
+    return (xx < 0 || xx >= a.W) ? -1 : xx * a.ldx;
+  };
 #pragma unroll
   for (int u = 0; u < B_PER; ++u) {
     const int id = tid + u * 256;
-    brow[u] = id / (TBN / 8);
-    bc8[u] = id % (TBN / 8);
-    const int j = bj + bc8[u] * 8;
-    bok[u] = j < a.RRC;
-    const int jj = bok[u] ? j : 0;
+    const int row = id / (TBN / 8), c8 = id % (TBN / 8);
+    bso[u] = img_off<NCB>(row, c8);
+    const int j = bj + c8 * 8;
+    const bool ok = j < a.RRC;
+    blim[u] = ok ? mlen - row : 0;
+    const int jj = ok ? j : 0;
     const int tap = jj / a.C;
-    bch[u] = jj - tap * a.C;
-    bry[u] = tap / a.R;
-    brx[u] = tap - bry[u] * a.R;
-    bpx[u] = pix_at(m_begin + brow[u], a.P, a.Q, m_end);
+    const int ry = tap / a.R;
+    by0[u] = ry - a.pad;
+    bx0[u] = tap - ry * a.R - a.pad;
+    const Pix px = pix_at(m_begin + row, a.P, a.Q, m_end);
+    bp[u] = px.p;
+    bq[u] = px.q;
+    bimg[u] = a.x + px.n * img_stride + (jj - tap * a.C);
+    byo[u] = yoff(bp[u], by0[u]);
+    bxo[u] = xoff(bq[u], bx0[u]);
   }
 
   uint4 ra[A_PER], rb[B_PER];
@@ -138,38 +158,55 @@ __global__ void __launch_bounds__(256) wgrad_tr_kernel(TrArgs a) {
 #pragma unroll
     for (int u = 0; u < A_PER; ++u) {
       ra[u] = make_uint4(0, 0, 0, 0);
-      if (apx[u].ok && aok[u])
-        ra[u] = *reinterpret_cast<const uint4*>(
-            a.dy + ((long)(apx[u].n * a.P + apx[u].p) * a.Q + apx[u].q) * a.ldy + bk + ac8[u] * 8);
+      if (mrel < alim[u]) ra[u] = *reinterpret_cast<const uint4*>(adp[u]);
     }
 #pragma unroll
     for (int u = 0; u < B_PER; ++u) {
       rb[u] = make_uint4(0, 0, 0, 0);
-      if (!bpx[u].ok || !bok[u]) continue;
-      int yy = bpx[u].p * a.stride - a.pad + bry[u], xx = bpx[u].q * a.stride - a.pad + brx[u];
-      if (a.reflect) {
-        yy = reflect_idx(yy, a.H);
-        xx = reflect_idx(xx, a.W);
-      } else if (yy < 0 || yy >= a.H || xx < 0 || xx >= a.W) {
-        continue;
-      }
-      rb[u] = *reinterpret_cast<const uint4*>(
-          a.x + ((long)(bpx[u].n * a.H + yy) * a.W + xx) * a.ldx + bch[u]);
+      if (mrel < blim[u] && (byo[u] | bxo[u]) >= 0)
+        rb[u] = *reinterpret_cast<const uint4*>(bimg[u] + (byo[u] + bxo[u]));
     }
   };
   auto store = [&](int buf) {
 #pragma unroll
-    for (int u = 0; u < A_PER; ++u)
-      *reinterpret_cast<uint4*>(&sA[buf][img_off<NCA>(arow[u], ac8[u])]) = ra[u];
+    for (int u = 0; u < A_PER; ++u) *reinterpret_cast<uint4*>(&sA[buf][aso[u]]) = ra[u];
 #pragma unroll
-    for (int u = 0; u < B_PER; ++u)
-      *reinterpret_cast<uint4*>(&sB[buf][img_off<NCB>(brow[u], bc8[u])]) = rb[u];
+    for (int u = 0; u < B_PER; ++u) *reinterpret_cast<uint4*>(&sB[buf][bso[u]]) = rb[u];
   };
-  auto advance = [&](long m0) {
+  // move the load cursor TBK pixels on.  row_step > 0: Q divides TBK and a
+  // step is that many whole rows (at most P), so q and the column offset stay
+  // and p wraps at most once; otherwise the general walk.
+  auto advance = [&]() {
+    mrel += TBK;
 #pragma unroll
-    for (int u = 0; u < A_PER; ++u) pix_adv(apx[u], TBK, a.P, a.Q, m0 + arow[u], m_end);
+    for (int u = 0; u < A_PER; ++u) adp[u] += astep;
+    const bool rows = a.row_step > 0;
 #pragma unroll
-    for (int u = 0; u < B_PER; ++u) pix_adv(bpx[u], TBK, a.P, a.Q, m0 + brow[u], m_end);
+    for (int u = 0; u < B_PER; ++u) {
+      int p = bp[u], q = bq[u];
+      const bf16_t* img = bimg[u];
+      if (rows) {
+        p += a.row_step;
+        if (p >= a.P) {
+          p -= a.P;
+          img += img_stride;
+        }
+      } else {
+        q += TBK;
+        while (q >= a.Q) {
+          q -= a.Q;
+          if (++p == a.P) {
+            p = 0;
+            img += img_stride;
+          }
+        }
+      }
+      bp[u] = p;
+      bq[u] = q;
+      bimg[u] = img;
+      byo[u] = yoff(p, by0[u]);
+      if (!rows) bxo[u] = xoff(q, bx0[u]);
+    }
   };
 
   // transposed-read offsets (elements, relative to a buffer): rows 8g+q and +4
@@ -198,7 +235,7 @@ __global__ void __launch_bounds__(256) wgrad_tr_kernel(TrArgs a) {
   if (m_begin < m_end) {
     load();
     store(0);
-    advance(m_begin + TBK);
+    advance();
   }
   __syncthreads();
   int cur = 0;
@@ -230,7 +267,7 @@ __global__ void __launch_bounds__(256) wgrad_tr_kernel(TrArgs a) {
     }
     if (more) {
       store(cur ^ 1);
-      advance(m0 + 2 * TBK);
+      advance();
     }
     __syncthreads();
     cur ^= 1;
@@ -299,8 +336,14 @@ int wgrad_tr_run(const void* x, int N, int H, int W, int C, int ldx, int K, int 
   a.pad = pad; a.reflect = reflect; a.P = P; a.Q = Q; a.ldy = ldy;
   a.M = N * P * Q;
   a.RRC = R * R * C;
+  // the kernel adds 32-bit offsets within one image to a 64-bit image pointer
+  if ((long)H * W * ldx > 0x7fffffffl) {
+    umamd::set_error("wgrad_tr: an image of %d x %d x %d elements exceeds 32-bit offsets", H, W, ldx);
+    return UM_ERR_ARG;
+  }
   const int tbk = wgrad_tr_tbk();
   a.m_per_split = ceil_div(ceil_div(a.M, splits), tbk) * tbk;
+  a.row_step = (tbk % Q == 0 && tbk / Q <= P) ? tbk / Q : 0;
   const int bm = wgrad_tr_bm(K);
   dim3 grid(ceil_div(K, bm), ceil_div(a.RRC, TBN), splits);
 #define UM_WTR(BM_, TBK_)                                                                 \
