@@ -58,9 +58,10 @@ enum {
 
 const char* um_last_error(void);
 int um_version(void);
-/* kernel-selection knobs (tests force code paths, tuning sweeps): "halo",
- * "halo_min_tiles", "small", "small_tiles", "split_below", "split_target",
- * "split_minsteps".  Returns the previous value, -1 for an unknown key. */
+/* kernel-selection values ("tuning keys"; tests force code paths, tuning
+ * sweeps): every key of the table in uncertainty-model_amd/csrc/knobs.h, the
+ * same keys UMAMD_TUNING="key=value,..." presets at load.  Returns the
+ * previous value, -1 for an unknown key. */
 int um_set_tuning(const char* key, int value);
 
 /* ---------------------------------------------------------------- conv ---
@@ -80,8 +81,7 @@ int um_conv_stats_parts(int M, int K);
 /* split-K workspace (bytes) the kernels want for a shape; 0 = no split.
  * Passing a smaller (or null) workspace is allowed: the split shrinks. */
 long um_conv_fwd_ws(int dtype, int N, int P, int Q, int K, int R, int C);
-long um_conv_dgrad_ws(int dtype, int N, int H, int W, int C, int R, int K, int stride);
-/* as um_conv_dgrad_ws, plus the padded-input buffer of the reflect data
+/* the data gradient's, plus the padded-input buffer of the reflect data
  * gradient's padded form (knob "pad_dgrad"): a zero-pad transposed conv onto
  * the (H+2p) x (W+2p) reflect-padded input, folded back onto dx */
 long um_conv_dgrad_ws_pad(int dtype, int N, int H, int W, int C, int R, int K, int stride,
@@ -121,12 +121,11 @@ int um_conv2d_wgrad(int dtype, int N, int H, int W, int C, int ldx, const void* 
                     int K, int R, int stride, int pad, int pad_mode, int P, int Q,
                     const void* dy, int ldy, float* slabs, int splits,
                     hipStream_t stream);
-/* sum slabs -> reference NCHW weight grad [Kreal][Creal][R][R] (f32), (+)= */
-int um_conv_wgrad_reduce(const float* slabs, int splits, int K, int Kreal, int R, int C,
-                         int Creal, float* dw, int accumulate, hipStream_t stream);
 
-/* segment variants: reference input channels [src0[i], src0[i]+len[i]) are
- * placed at packed channels [dst0[i], ...) (host arrays, nseg <= 4); the rest
+/* um_conv_wgrad_reduce_seg: sum slabs -> reference NCHW weight grad
+ * [Kreal][Creal][R][R] (f32), (+)=.  Segments (both entries): reference input
+ * channels [src0[i], src0[i]+len[i]) are placed at packed channels
+ * [dst0[i], ...) (host arrays, nseg <= 4; nseg = 0: channel c at c); the rest
  * of the packed channels are zero.  Keeps concat sources 8-channel aligned. */
 int um_conv_wgrad_reduce_seg(const float* slabs, int splits, int K, int Kreal, int R, int C,
                              int Creal, float* dw, int accumulate, int nseg, const int* src0,
@@ -244,11 +243,10 @@ int um_bn_fold(const float* w, const float* bias, int K, int Creal, int R, const
                const float* beta, const float* running_mean, const float* running_var,
                float eps, float* w_out, float* b_out, hipStream_t stream);
 /* pool_parts (optional, SE squeeze of decoder.py:124-136 fused in): per-block
- * channel sums of a, [um_bn_fwd_pool_parts(M, HW)][C], HW = pixels per image */
-int um_bn_fwd_pool_parts(long M, long HW);
-/* the same for a C-channel layer (the forward pass may split small layers
- * into 64-channel slices with their own row blocking): the pool row count
- * um_bn_elu_fwd / um_bn_elu_fwd_slots write */
+ * channel sums of a, [um_bn_fwd_pool_parts_c(M, HW, C)][C], HW = pixels per
+ * image (the forward pass may split small layers into 64-channel slices with
+ * their own row blocking): the pool row count um_bn_elu_fwd /
+ * um_bn_elu_fwd_slots write */
 int um_bn_fwd_pool_parts_c(long M, long HW, int C);
 int um_bn_elu_fwd(int dtype, long M, int C, const void* y, int ldy, const float* scale,
                   const float* shift, void* a, int lda, int apply_elu, long HW, float* pool_parts,
@@ -364,7 +362,6 @@ int um_merge_wgrad(const float* parts, int nparts, int nsrc, const int* widx,
                    const float* w, float* dw, int nw, int accumulate, hipStream_t stream);
 int um_image_to_nhwc(int dtype, const float* x, int N, int C, int H, int W, int Cp,
                      void* out, hipStream_t stream);
-int um_axpy(int dtype, long n, float alpha, const void* x, void* y, hipStream_t stream);
 /* d/dlogit of scale*sigmoid(logit): disp head, reference model/layers/decoder.py:246 */
 int um_sigmoid_scale_bwd(int dtype, long M, int C, const float* d, int ldd, const float* dd,
                          int lddd, float scale, void* dlogit, int ldo, hipStream_t stream);
@@ -562,8 +559,6 @@ int um_spars_curve(const float* sorted_vals, int nseg, int L, int steps, double*
  * torch.optim.Adam step, reference train/train.py:228-229.
  */
 int um_adam_chunk(void);
-int um_adam_step(const void* table, const void* chunks, int nchunks, float lr, float beta1,
-                 float beta2, float eps, float weight_decay, int step, hipStream_t stream);
 /* graph-replayable: *dstep += 1 on the device, bias corrections from it; lr from *dlr if non-null */
 int um_adam_step_dev(const void* table, const void* chunks, int nchunks, float lr,
                      const float* dlr, float beta1, float beta2, float eps, float weight_decay,

@@ -46,6 +46,113 @@ def test_host_queries_without_gpu():
     assert query('um_colred_ws', 1000, 32, 2) > 0
 
 
+def _header_decls():
+    """{name: (return type, [argument types])} of include/umamd.h, comments
+    stripped, each type reduced to its kind: 'ptr', 'cstr' (const char*) or
+    the scalar's name"""
+    src = open(os.path.join(REPO, 'include', 'umamd.h')).read()
+    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
+    src = re.sub(r'//[^\n]*', '', src)
+
+    def kind(t, is_arg):
+        tok = t.replace('*', ' * ').split()
+        if '*' in tok:
+            return 'cstr' if tok[:3] == ['const', 'char', '*'] and tok.count('*') == 1 else 'ptr'
+        tok = [w for w in tok if w != 'const']
+        if is_arg and len(tok) > 1:  # drop the parameter name
+            tok = tok[:-1]
+        return ' '.join(tok)
+
+    out = {}
+    for ret, name, args in re.findall(r'([\w \*]+?)\b(um_\w+)\s*\(([^)]*)\)\s*;', src):
+        args = args.strip()
+        alist = [] if args in ('', 'void') else [kind(a, True) for a in args.split(',')]
+        out[name] = (kind(ret, False), alist)
+    return out
+
+
+def test_binding_signatures_match_header():
+    """every _SIG entry against its declaration: return type, argument count
+    and argument kinds (a slip passes every CPU test and corrupts a GPU call)"""
+    import ctypes
+    from umamd import _lib
+    to_c = {'ptr': ctypes.c_void_p, 'cstr': ctypes.c_char_p, 'int': ctypes.c_int,
+            'long': ctypes.c_long, 'float': ctypes.c_float, 'double': ctypes.c_double,
+            'hipStream_t': 's'}
+    decls = _header_decls()
+    assert sorted(decls) == _header_symbols()
+    bad = []
+    for name, (res, args) in _lib._SIG.items():
+        hret, hargs = decls[name]
+        want = (to_c[hret], [to_c[a] for a in hargs])
+        if (res, list(args)) != want:
+            bad.append((name, (res, list(args)), want))
+    assert not bad, bad
+
+
+# key -> default: the table of csrc/knobs.h, written out
+TUNING_DEFAULTS = {
+    'small': 1, 'small_tiles': 1024, 'split_below': 600, 'split_target': 1024,
+    'split_minsteps': 4, 'glds_split_below': 256, 'glds_split_target': 512, 'halo': 1,
+    'halo_min_tiles': 256, 'halo_max_nc': 192, 'odd_bn': 1, 'bk64': 3, 'glds': 5, 'glds_deep': 3,
+    'glds_deep_blocks': 256, 'xcd_col': 0, 'tappack': 1, 'cls4': 1, 'cls_glds': 3, 'pad_dgrad': 1,
+    'fold_split_nc': 64, 'halo_pf2': 0, 'halo_persist': 1, 'halo_grid': 0, 'halo_res_kb': 48,
+    'halo_staged': 1, 'border_valu': 1, 's1x1': 1, 's1x1_small': 1, 'cat_fused': 0, 'merge_ns': 1,
+    'colred_single': 131072, 'colred_per': 16384, 'wtr_tbk': 32, 'w1x1': 1, 'border_split': 1,
+    'up2_valu': 1, 'wsplit_blocks': 0, 'wred_t': 1, 'bn_bwd_rows_max': 1024, 'bn_slice': 1,
+    'dh_fwd': 0, 'dh_fwd128': 1, 'dh_dgrad': 1,
+}
+
+
+def test_every_tuning_key_round_trips():
+    from umamd._lib import UmamdError, lib, tuning
+    assert len(TUNING_DEFAULTS) == 44
+    L = lib()
+    for key, d in TUNING_DEFAULTS.items():
+        assert L.um_set_tuning(key.encode(), d + 1) == d, key
+        assert L.um_set_tuning(key.encode(), d) == d + 1, key
+    assert L.um_set_tuning(b'nope', 1) == -1
+    with pytest.raises(UmamdError):
+        with tuning(bn_slice=0, nope=1):
+            pass
+    assert L.um_set_tuning(b'bn_slice', 1) == 1  # what tuning() set before the bad key is restored
+    with pytest.raises(ZeroDivisionError):
+        with tuning(halo=0):
+            1 / 0
+    assert L.um_set_tuning(b'halo', 1) == 1  # restored when the body raises
+
+
+def test_tuning_env_reaches_the_table():
+    import sys
+    code = ('from umamd._lib import lib; L = lib(); '
+            "print(L.um_set_tuning(b'bn_slice', 1), L.um_set_tuning(b'halo_res_kb', 48), "
+            "L.um_set_tuning(b'halo', 1))")
+    env = dict(os.environ, UMAMD_TUNING='bn_slice=0,halo_res_kb=7', PYTHONPATH=PKG)
+    out = subprocess.run([sys.executable, '-c', code], env=env, capture_output=True, text=True,
+                         check=True).stdout
+    assert out.split() == ['0', '7', '1']
+
+
+def test_tuning_keys_take_effect_at_run_time():
+    """the keys that used to be frozen at first use, seen through the host
+    queries that size buffers (values measured on the library before the
+    table, its keys preset through UMAMD_TUNING)"""
+    from umamd._lib import query, tuning
+    cases = [
+        (('um_colred_ws', 1000, 32, 2), 512, dict(colred_single=1), 2048),
+        (('um_bn_fwd_pool_parts_c', 4096, 512, 128), 128, dict(bn_slice=0), 256),
+        (('um_bn_bwd_parts', 1 << 20), 1024, dict(bn_bwd_rows_max=64), 16384),
+        # f32: the generic kernel's fixed 768-workgroup target, no CU count in it
+        (('um_conv_wgrad_splits', 0, 8, 128, 256, 32, 32, 32, 7, 1, 3, 0, 128, 256, 32), 60,
+         dict(wsplit_blocks=64), 5),
+    ]
+    for q, dflt, knobs, with_knob in cases:
+        assert query(*q) == dflt, q
+        with tuning(**knobs):
+            assert query(*q) == with_knob, (q, knobs)
+        assert query(*q) == dflt, q
+
+
 def test_kernel_call_fails_loudly_on_cpu_tensor():
     import torch
     from umamd import functional as U

@@ -34,26 +34,6 @@ def _nchw(x):
     return x.detach().permute(0, 3, 1, 2).float().cpu()
 
 
-class _tuning:
-    """um_set_tuning keys for the duration of a block"""
-
-    def __init__(self, **knobs):
-        self.knobs = {k.encode(): v for k, v in knobs.items()}
-
-    def __enter__(self):
-        from umamd._lib import lib
-        self.old = {}
-        for k, v in self.knobs.items():
-            self.old[k] = lib().um_set_tuning(k, v)
-            assert self.old[k] != -1, k
-        return self
-
-    def __exit__(self, *exc):
-        from umamd._lib import lib
-        for k, v in self.old.items():
-            lib().um_set_tuning(k, v)
-
-
 # split-K forced on (every grid below 256 tiles splits towards 512 blocks,
 # >= minsteps k-steps per split) or off; the 1x1 cases have 1 or 2 k-steps, so
 # only a one-step minimum splits them at all
@@ -88,7 +68,7 @@ def _fwd_dgrad_case(C, K, R, mode, N=2, H=9, W=7):
 
 def _run_fwd_dgrad(C, K, R, mode, split, extra=None):
     from umamd import functional as U
-    from umamd._lib import PAD_REFLECT, PAD_ZERO
+    from umamd._lib import PAD_REFLECT, PAD_ZERO, tuning
     N, H, W = 2, 9, 7  # M = 126: the last 64-row tile has out-of-range rows
     w, x, dy, ref_y, ref_dx = _fwd_dgrad_case(C, K, R, mode)
     pad = (R - 1) // 2
@@ -98,7 +78,7 @@ def _run_fwd_dgrad(C, K, R, mode, split, extra=None):
     for glds in (5, 0):  # LDS-DMA 8-wave 64x64 tiles, then the register path
         knobs = dict(halo=0, glds=glds, **_split_knobs(split, R))
         knobs.update(extra or {})
-        with _tuning(**knobs):
+        with tuning(**knobs):
             y = U._conv_fwd(_nhwc(x).to(DT), wf, None, K, R, 1, pad, pm, out_dtype=torch.float32)
             dx = U._conv_dgrad(_nhwc(dy).to(DT), wT, (N, H, W, C), K, R, 1, pad, pm)
             torch.cuda.synchronize()
@@ -139,7 +119,7 @@ def test_glds_cursor_stride2_classes(split):
     """stride-2 data gradient, C = K = 64 on 8x8 -> 16x16: the four parity
     classes as one launch of LDS-DMA tiles (1, 2, 2 and 4 one-step taps)"""
     from umamd import functional as U
-    from umamd._lib import PAD_ZERO
+    from umamd._lib import PAD_ZERO, tuning
     C = K = 64
     N, H, W, R, pad = 2, 16, 16, 3, 1
     g = torch.Generator().manual_seed(17)
@@ -151,7 +131,7 @@ def test_glds_cursor_stride2_classes(split):
     outs = []
     for cls_glds in (3, 0):  # LDS-DMA tiles, then the 256-row register tiles
         knobs = dict(cls4=1, cls_glds=cls_glds, **_split_knobs(split, 1))
-        with _tuning(**knobs):
+        with tuning(**knobs):
             dx = U._conv_dgrad(_nhwc(dy).to(DT), wT, (N, H, W, C), K, R, 2, pad, PAD_ZERO)
             torch.cuda.synchronize()
         outs.append(_nchw(dx))

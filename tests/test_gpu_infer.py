@@ -80,7 +80,7 @@ def _run_op(case, dtype, knobs, batch_norm=True, creal=None, cout_pad=0):
     F.elu(batch_norm_eval(conv(pad(x)))) from the UNFOLDED parameters"""
     from umamd import _lib as L
     from umamd import functional as U
-    from umamd._lib import call, lib, ptr
+    from umamd._lib import call, ptr, tuning
     Cin, Cout, k, stride, mode, H, W = case
     N, pad = 2, (k - 1) // 2
     g = torch.Generator().manual_seed(7)
@@ -111,15 +111,11 @@ def _run_op(case, dtype, knobs, batch_norm=True, creal=None, cout_pad=0):
     P, Q = ref.shape[2], ref.shape[3]
     ld = Cout + cout_pad
     out = torch.zeros(N, P, Q, ld, dtype=dtype, device=DEV)
-    old = {kk: lib().um_set_tuning(kk, v) for kk, v in knobs.items()}
-    try:
+    with tuning(**knobs):
         U._conv_fwd(xd, wf, bfold, Cout, k, stride, pad,
                     L.PAD_REFLECT if mode == 'reflect' else L.PAD_ZERO, out_dtype=dtype,
                     epi=L.EPI_ELU, out=out, creal=creal)
         torch.cuda.synchronize()
-    finally:
-        for kk, v in old.items():
-            lib().um_set_tuning(kk, v)
     got = out[..., :Cout].permute(0, 3, 1, 2).double().cpu()
     err = float((got - ref).abs().max() / ref.abs().max())
     print(f'{case} {dtype} {knobs}: max-abs/max-ref {err:.3e}')
@@ -127,7 +123,7 @@ def _run_op(case, dtype, knobs, batch_norm=True, creal=None, cout_pad=0):
     return out
 
 
-GEMM_OFF = {b'halo': 0, b's1x1': 0, b's1x1_small': 0}
+GEMM_OFF = {'halo': 0, 's1x1': 0, 's1x1_small': 0}
 DTYPES = [torch.float32, torch.bfloat16]
 
 
@@ -135,7 +131,7 @@ DTYPES = [torch.float32, torch.bfloat16]
 @pytest.mark.parametrize('case', [(24, 40, 1, 1, 'zero', 6, 10), (40, 48, 3, 1, 'reflect', 10, 14),
                                   (8, 32, 7, 2, 'zero', 16, 24), (16, 8, 3, 1, 'reflect', 4, 6)])
 def test_elu_epilogue_register_gemm(case, dtype):
-    _run_op(case, dtype, {**GEMM_OFF, b'glds': 0})
+    _run_op(case, dtype, {**GEMM_OFF, 'glds': 0})
 
 
 @pytest.mark.parametrize('dtype', DTYPES)
@@ -158,8 +154,8 @@ def test_elu_epilogue_splitk(case, dtype):
 def test_elu_epilogue_halo(case, res, hgrid, staged):
     """the halo kernel forced on: streamed / resident weights, scalar and
     LDS-staged 16-byte stores (ELU applied before staging), persistent grid"""
-    _run_op(case, torch.bfloat16, {b'halo_min_tiles': 1, b'halo_res_kb': res,
-                                   b'halo_staged': staged, b'halo_grid': hgrid})
+    _run_op(case, torch.bfloat16, {'halo_min_tiles': 1, 'halo_res_kb': res,
+                                   'halo_staged': staged, 'halo_grid': hgrid})
 
 
 @pytest.mark.parametrize('dtype', DTYPES)

@@ -85,14 +85,9 @@ def test_conv_bn_elu_halo(case, pf2, res, hgrid):
     0: at most that many workgroups per column block, so each takes several
     tiles and prefetches the next one's halo (knob halo_grid); forward, BN
     statistics and data gradient"""
-    from umamd._lib import lib
-    knobs = {b'halo_min_tiles': 1, b'halo_pf2': pf2, b'halo_res_kb': res, b'halo_grid': hgrid}
-    old = {k: lib().um_set_tuning(k, v) for k, v in knobs.items()}
-    try:
+    from umamd._lib import tuning
+    with tuning(halo_min_tiles=1, halo_pf2=pf2, halo_res_kb=res, halo_grid=hgrid):
         test_conv_bn_elu(case, torch.bfloat16)
-    finally:
-        for k, v in old.items():
-            lib().um_set_tuning(k, v)
 
 
 @pytest.mark.parametrize('case', HALO_CASES)
@@ -100,14 +95,9 @@ def test_conv_bn_elu_halo_persist_slots(case):
     """persistent halo workgroups (2 per column block) with the BN statistics
     in f64 slots: each tile adds its own slot rows"""
     from umamd import functional as U
-    from umamd._lib import lib
-    old = lib().um_set_tuning(b'halo_min_tiles', 1)
-    old_g = lib().um_set_tuning(b'halo_grid', 2)
-    try:
+    from umamd._lib import tuning
+    with tuning(halo_min_tiles=1, halo_grid=2):
         test_conv_bn_elu(case, torch.bfloat16, arena=U.StatArena())
-    finally:
-        lib().um_set_tuning(b'halo_min_tiles', old)
-        lib().um_set_tuning(b'halo_grid', old_g)
 
 
 @pytest.mark.parametrize('case', CONV_CASES)
@@ -117,12 +107,9 @@ def test_conv_bn_elu_slots(case, dtype):
     same bars as the partial-row reductions, with the halo kernel forced on
     for bf16 so its slot epilogue is covered too"""
     from umamd import functional as U
-    from umamd._lib import lib
-    old = lib().um_set_tuning(b'halo_min_tiles', 1)
-    try:
+    from umamd._lib import tuning
+    with tuning(halo_min_tiles=1):
         test_conv_bn_elu(case, dtype, arena=U.StatArena())
-    finally:
-        lib().um_set_tuning(b'halo_min_tiles', old)
 
 
 @pytest.mark.parametrize('case', CONV_CASES)
@@ -591,7 +578,7 @@ def test_up2_concat_adjoint(h, w, gated, C):
 # data gradient through the 48/96/160-wide tiles (NC = the conv's input
 # channels: the decoder-concat counts 40/88/160/168/320), against f64 torch on
 # the same bf16/f32 operands, with each shape checked under the odd-width tile
-# and under the 64/128-wide tile it replaces (UMAMD_IG_ODD_BN = 0), with the
+# and under the 64/128-wide tile it replaces (tuning key odd_bn = 0), with the
 # 64x64 deep-layer plan switched off so the 128-row plan is taken.
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize('case', [(40, 32, 3, 2, 96, 128), (88, 64, 3, 2, 128, 128),
@@ -599,7 +586,7 @@ def test_up2_concat_adjoint(h, w, gated, C):
                                   (320, 256, 3, 2, 64, 96), (72, 32, 1, 2, 128, 160)])
 def test_dgrad_odd_tiles(dtype, case):
     from umamd import functional as U
-    from umamd._lib import PAD_ZERO, lib
+    from umamd._lib import PAD_ZERO, tuning
     C, K, R, N, H, W = case
     pad = (R - 1) // 2
     g = torch.Generator().manual_seed(11)
@@ -611,16 +598,9 @@ def test_dgrad_odd_tiles(dtype, case):
     _, wT = U._pack(w.to(DEV), C, dtype, wf=False)
     outs = []
     for odd in (1, 0):
-        old = lib().um_set_tuning(b'odd_bn', odd)
-        old_h = lib().um_set_tuning(b'halo', 0)
-        old_s = lib().um_set_tuning(b'small', 0)
-        try:
+        with tuning(odd_bn=odd, halo=0, small=0):
             dx = U._conv_dgrad(_nhwc(dy).to(dtype), wT, (N, H, W, C), K, R, 1, pad, PAD_ZERO)
             torch.cuda.synchronize()
-        finally:
-            lib().um_set_tuning(b'odd_bn', old)
-            lib().um_set_tuning(b'halo', old_h)
-            lib().um_set_tuning(b'small', old_s)
         outs.append(_nchw(dx))
     tol = 1e-5 if dtype == torch.float32 else 1e-2
     for o in outs:
@@ -649,7 +629,7 @@ def test_dgrad_reflect(dtype, case, border_valu):
     """border_valu: the split form's reflect fold as the VALU border pass
     (2: every shape) or as the register GEMM's border-list mode (0)"""
     from umamd import functional as U
-    from umamd._lib import PAD_REFLECT, lib
+    from umamd._lib import PAD_REFLECT, tuning
     C, K, R, N, H, W, accumulate = case
     pad = 1
     g = torch.Generator().manual_seed(5)
@@ -669,20 +649,11 @@ def test_dgrad_reflect(dtype, case, border_valu):
     # the padded input + reflect fold pass) forced
     for hmin, snc, pd in ((256, 64, 1), (1, 64, 1), (256, 0, 0), (256, 4096, 1), (256, 64, 2),
                           (1, 64, 2)):
-        old = lib().um_set_tuning(b'halo_min_tiles', hmin)
-        old_s = lib().um_set_tuning(b'fold_split_nc', snc)
-        old_p = lib().um_set_tuning(b'pad_dgrad', pd)
-        old_b = lib().um_set_tuning(b'border_valu', border_valu)
-        try:
+        with tuning(halo_min_tiles=hmin, fold_split_nc=snc, pad_dgrad=pd, border_valu=border_valu):
             dx = _nhwc(dx0).to(dtype).contiguous() if accumulate else None
             out = U._conv_dgrad(_nhwc(dy).to(dtype), wT, (N, H, W, C), K, R, 1, pad, PAD_REFLECT,
                                 dx=dx, accumulate=accumulate)
             torch.cuda.synchronize()
-        finally:
-            lib().um_set_tuning(b'halo_min_tiles', old)
-            lib().um_set_tuning(b'fold_split_nc', old_s)
-            lib().um_set_tuning(b'pad_dgrad', old_p)
-            lib().um_set_tuning(b'border_valu', old_b)
         err = _rel(_nchw(out), ref)
         print(f'dgrad_reflect {case} {dtype} halo_min_tiles={hmin} fold_split_nc={snc} '
               f'pad_dgrad={pd}: rel {err:.3e}')
@@ -700,7 +671,7 @@ def test_dgrad_reflect(dtype, case, border_valu):
 @pytest.mark.parametrize('xcd_col', [0, 2])
 def test_glds_stage_depth(case, deep, split_below, xcd_col):
     from umamd import functional as U
-    from umamd._lib import PAD_ZERO, lib
+    from umamd._lib import PAD_ZERO, tuning
     C, K, R, N, H, W = case
     pad = (R - 1) // 2
     dtype = torch.bfloat16
@@ -712,17 +683,12 @@ def test_glds_stage_depth(case, deep, split_below, xcd_col):
     ref_y = F.conv2d(xq, wq, padding=pad)
     ref_dx = torch.nn.grad.conv2d_input((N, C, H, W), wq, dyq, padding=pad)
     wf, wT = U._pack(w.to(DEV), C, dtype)
-    knobs = {b'glds_deep': deep, b'glds_deep_blocks': 1024, b'glds_split_below': split_below,
-             b'halo': 0, b'xcd_col': xcd_col}
-    old = {k: lib().um_set_tuning(k, v) for k, v in knobs.items()}
-    try:
+    with tuning(glds_deep=deep, glds_deep_blocks=1024, glds_split_below=split_below, halo=0,
+                xcd_col=xcd_col):
         y = U._conv_fwd(_nhwc(x).to(dtype), wf, None, K, R, 1, pad, PAD_ZERO,
                         out_dtype=torch.float32)
         dx = U._conv_dgrad(_nhwc(dy).to(dtype), wT, (N, H, W, C), K, R, 1, pad, PAD_ZERO)
         torch.cuda.synchronize()
-    finally:
-        for k, v in old.items():
-            lib().um_set_tuning(k, v)
     assert _rel(_nchw(y), ref_y) < 1e-5
     assert _rel(_nchw(dx), ref_dx) < 1e-2
 
@@ -740,7 +706,7 @@ def test_glds_stage_depth(case, deep, split_below, xcd_col):
 @pytest.mark.parametrize('pack', [0, 3])
 def test_tappack(dtype, case, pack):
     from umamd import functional as U
-    from umamd._lib import PAD_REFLECT, PAD_ZERO, lib
+    from umamd._lib import PAD_REFLECT, PAD_ZERO, tuning
     C, K, R, stride, mode, N, H, W = case
     pad = (R - 1) // 2
     g = torch.Generator().manual_seed(21)
@@ -755,14 +721,11 @@ def test_tappack(dtype, case, pack):
     (ref_y * dyq).sum().backward()
     wf, wT = U._pack(w.to(DEV), C, dtype)
     pm = PAD_REFLECT if mode == 'reflect' else PAD_ZERO
-    old = lib().um_set_tuning(b'tappack', pack)
-    try:
+    with tuning(tappack=pack):
         y = U._conv_fwd(_nhwc(x).to(dtype), wf, None, K, R, stride, pad, pm,
                         out_dtype=torch.float32)
         dx = U._conv_dgrad(_nhwc(dy).to(dtype), wT, (N, H, W, C), K, R, stride, pad, pm)
         torch.cuda.synchronize()
-    finally:
-        lib().um_set_tuning(b'tappack', old)
     tol = 1e-5 if dtype == torch.float32 else 1e-2
     assert _rel(_nchw(y), ref_y) < 1e-5
     assert _rel(_nchw(dx), xr.grad) < tol
@@ -783,7 +746,7 @@ def test_tappack(dtype, case, pack):
 @pytest.mark.parametrize('mode', [(0, 3), (1, 3), (1, 1), (1, 0)])
 def test_dgrad_stride2_classes(case, mode):
     from umamd import functional as U
-    from umamd._lib import PAD_ZERO, lib
+    from umamd._lib import PAD_ZERO, tuning
     C, K, R, N, H, W = case
     cls4, glds = mode
     pad = (R - 1) // 2
@@ -796,14 +759,9 @@ def test_dgrad_stride2_classes(case, mode):
     wq, dyq = w.to(dtype).double(), dy.to(dtype).double()
     ref = torch.nn.grad.conv2d_input((N, C, H, W), wq, dyq, stride=2, padding=pad)
     _, wT = U._pack(w.to(DEV), C, dtype, wf=False)
-    old = lib().um_set_tuning(b'cls4', cls4)
-    old_g = lib().um_set_tuning(b'cls_glds', glds)
-    try:
+    with tuning(cls4=cls4, cls_glds=glds):
         dx = U._conv_dgrad(_nhwc(dy).to(dtype), wT, (N, H, W, C), K, R, 2, pad, PAD_ZERO)
         torch.cuda.synchronize()
-    finally:
-        lib().um_set_tuning(b'cls4', old)
-        lib().um_set_tuning(b'cls_glds', old_g)
     assert _rel(_nchw(dx), ref) < 1e-2
 
 
@@ -972,7 +930,7 @@ def test_conv_bn_elu_ybf16(case, monkeypatch):
                                   (1, 129, 131, 96, 32, 'dgrad'), (2, 64, 128, 64, 192, 'bias'),
                                   (1, 128, 130, 192, 64, 'dgrad'), (2, 64, 128, 128, 128, 'up2stats')])
 def test_stream1x1(case):
-    _check_1x1(case, b's1x1')
+    _check_1x1(case, 's1x1')
 
 
 # the small-M 1x1 kernel (stream1x1.hip s1x1_small_kernel, tuning key
@@ -987,13 +945,13 @@ def test_stream1x1(case):
                                   (2, 16, 32, 320, 64, 'bias'), (1, 8, 16, 64, 32, 'bias'),
                                   (1, 62, 64, 256, 512, 'up2stats'), (2, 8, 32, 512, 48, 'residual')])
 def test_s1x1_small(case):
-    _check_1x1(case, b's1x1_small')
+    _check_1x1(case, 's1x1_small')
 
 
 def _check_1x1(case, key):
     from umamd import functional as U
     from umamd import _lib as L
-    from umamd._lib import PAD_ZERO, call, lib, ptr
+    from umamd._lib import PAD_ZERO, call, ptr, tuning
     N, H, W, C, K, mode = case
     g = torch.Generator().manual_seed(11)
     x = (torch.rand(N, H, W, C, generator=g) - 0.3).to(torch.bfloat16).to(DEV)
@@ -1027,13 +985,10 @@ def _check_1x1(case, key):
         _, wTd = U._pack(wfw, K, torch.bfloat16)
         outs = []
         for flag in (1, 0):
-            old = lib().um_set_tuning(key, flag)
-            try:
+            with tuning(**{key: flag}):
                 dx = prev[..., :K].contiguous().clone()
                 U._conv_dgrad(x, wTd, (N, H, W, K), C, 1, 1, 0, PAD_ZERO, dx=dx, accumulate=True)
                 torch.cuda.synchronize()
-            finally:
-                lib().um_set_tuning(key, old)
             outs.append(dx.double())
         ref = prev[..., :K].double() + torch.einsum('nhwc,ck->nhwk', x.double(),
                                                     wfw.to(torch.bfloat16).double()[:, :, 0, 0])
@@ -1041,12 +996,9 @@ def _check_1x1(case, key):
         return
     outs = []
     for flag in (1, 0):
-        old = lib().um_set_tuning(key, flag)
-        try:
+        with tuning(**{key: flag}):
             outs.append(run())
             torch.cuda.synchronize()
-        finally:
-            lib().um_set_tuning(key, old)
     ref = torch.einsum('nhwc,kc->nhwk', x.double(), wq)
     if mode != 'f32':
         ref = ref + bias.double()

@@ -57,22 +57,8 @@ int um_adam_chunk(void) { return CHUNK; }
 
 // table: device array of n_entries x {p, g, m, v, numel} (5 x 8 bytes each)
 // chunks: device int2 array (entry, chunk)
-int um_adam_step(const void* table, const void* chunks, int nchunks, float lr, float beta1,
-                 float beta2, float eps, float weight_decay, int step, hipStream_t st) {
-  UM_CHECK_ARG(step >= 1, "um_adam_step: step %d", step);
-  const double bc1 = 1.0 - pow((double)beta1, step);
-  const double bc2 = 1.0 - pow((double)beta2, step);
-  const int blocks = nchunks < 8192 ? nchunks : 8192;
-  if (blocks == 0) return UM_OK;
-  hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, st, (const AdamEntry*)table,
-                     (const int2*)chunks, nchunks, (float)(lr / bc1), beta1, beta2,
-                     (float)(1.0 / sqrt(bc2)), eps, weight_decay, nullptr, nullptr);
-  UM_LAUNCH_CHECK();
-  return UM_OK;
-}
-
-// Graph-replayable variant: increments the device step counter, then updates
-// with bias corrections computed from it; lr read from dlr (device) if given.
+// Graph-replayable: increments the device step counter, then updates with
+// bias corrections computed from it; lr read from dlr (device) if given.
 int um_adam_step_dev(const void* table, const void* chunks, int nchunks, float lr,
                      const float* dlr, float beta1, float beta2, float eps, float weight_decay,
                      int* dstep, hipStream_t st) {

@@ -18,6 +18,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "knobs.h"
 
 namespace {
 
@@ -216,7 +217,7 @@ __global__ void __launch_bounds__(256) bn_elu_fwd_kernel(
 // blocks, 16..max rows) with the cap as a tuning key (bn_bwd_rows_max,
 // default 1024 = rows_per_part)
 static int bn_bwd_rows(long M) {
-  static const int cap = (int)umamd::tuning_env("bn_bwd_rows_max", 1024);
+  const int cap = umamd::knobs().bn_bwd_rows_max;
   const long r = (M + 511) / 512;
   int p = 16;
   while (p < r && p < cap) p <<= 1;
@@ -555,7 +556,7 @@ struct Slices {
   int cs, ns;
 };
 Slices bn_slices(long M, int C) {
-  static const int on = (int)umamd::tuning_env("bn_slice", 1);
+  const int on = umamd::knobs().bn_slice;
   if (!on || C < 128 || C % 64 || M * C > (8l << 20)) return {C, 1};
   return {64, C / 64};
 }
@@ -582,10 +583,6 @@ int bwd_rows_c(long M, int C) {
 }  // namespace
 
 extern "C" {
-
-int um_bn_fwd_pool_parts(long M, long HW) {
-  return HW > 0 && M % HW == 0 ? (int)(M / fwd_rows(M, HW)) : 0;
-}
 
 int um_bn_fwd_pool_parts_c(long M, long HW, int C) {
   return HW > 0 && M % HW == 0 ? (int)(M / fwd_rows_c(M, HW, C)) : 0;

@@ -20,11 +20,9 @@ typedef __hip_bfloat16 bf16_t;
 // ------------------------------------------------------------ error state --
 namespace umamd {
 void set_error(const char* fmt, ...);
-// Tuning values for sweeps: the ONE environment variable UMAMD_TUNING holds
-// "key=value,key=value" (keys as um_set_tuning's); a key not listed there
-// gives ``dflt``.  Read once per key by each caller (static initialisers).
-long tuning_env(const char* key, long dflt);
 }  // namespace umamd
+// (the tuning keys -- UMAMD_TUNING, um_set_tuning -- are the table in knobs.h,
+// read where a decision is made through umamd::knobs())
 
 #define UM_CHECK_ARG(cond, ...)                    \
   do {                                             \

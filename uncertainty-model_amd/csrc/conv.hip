@@ -23,6 +23,7 @@
 
 #include "common.h"
 #include "igemm.h"
+#include "knobs.h"
 #include "wgrad_halo.h"
 #include "wgrad_tr.h"
 
@@ -483,7 +484,7 @@ __global__ void __launch_bounds__(W1_NT) wgrad_1x1_kernel(WgradArgs a) {
 
 static bool wgrad_1x1_ok(int dtype, int C, int K, int R, int stride, int pad, int ldx, int ldy) {
   auto p2 = [](int v) { return v == 8 || v == 16 || v == 32 || v == 64; };
-  static const bool on = umamd::tuning_env("w1x1", 1) != 0;  // read once (common.h)
+  const bool on = umamd::knobs().w1x1 != 0;
   return dtype == UM_BF16 && on && R == 1 && stride == 1 && pad == 0 &&
          p2(C) && p2(K) && K * C <= W1_MAX && ldx % 8 == 0 && ldy % 8 == 0;
 }
@@ -924,12 +925,12 @@ __global__ void __launch_bounds__(256) reflect_fold_kernel(const T* __restrict__
 // -- except where the split form's zero-pad pass runs on the halo kernel (its
 // 64..192-wide column blocks: 128x256 C88 and 64x128 C168 decoder layers)
 bool split_form(int dtype, int N, int H, int W, int C, int R) {
-  return C <= umamd::igemm_fold_split_nc() || umamd::igemm_halo_dgrad(dtype, N, H, W, C, R);
+  return C <= umamd::knobs().fold_split_nc || umamd::igemm_halo_dgrad(dtype, N, H, W, C, R);
 }
 
 bool pad_dgrad_applies(int dtype, int N, int C, int R, int pad, int pad_mode, int stride, int P,
                        int Q, int H, int W) {
-  const int kn = umamd::igemm_pad_dgrad();
+  const int kn = umamd::knobs().pad_dgrad;
   if (kn == 0 || pad_mode != UM_PAD_REFLECT || stride != 1 || pad <= 0 || pad >= H || pad >= W) return false;
   if (P != H || Q != W || C % 8) return false;
   return kn == 2 || !split_form(dtype, N, H, W, C, R);
@@ -943,43 +944,8 @@ long pad_dgrad_bytes(int dtype, int N, int H, int W, int C, int R, int K, int pa
   return buf + umamd::igemm_ws_bytes(dtype, (int)(N * Hp * Wp), C, R * R, K);
 }
 
-}  // namespace
-
-extern "C" {
-
-long um_conv_dgrad_ws_pad(int dtype, int N, int H, int W, int C, int R, int K, int stride, int pad,
-                          int pad_mode) {
-  const long base = um_conv_dgrad_ws(dtype, N, H, W, C, R, K, stride);
-  if (pad_dgrad_applies(dtype, N, C, R, pad, pad_mode, stride, H, W, H, W))
-    return std::max(base, pad_dgrad_bytes(dtype, N, H, W, C, R, K, pad, nullptr));
-  // split form of a reflect data gradient: the border-list GEMM of the fold
-  // splits its k-loop too (a few thousand rows x 9 taps: unsplit, 96-256
-  // workgroups ran 24-53 us behind a 30-87 us main pass), unless the fold is
-  // the VALU pass (um_conv2d_dgrad)
-  static const int border_split = (int)umamd::tuning_env("border_split", 1);
-  if (border_split && pad_mode == UM_PAD_REFLECT && pad > 0 && stride == 1 &&
-      split_form(dtype, N, H, W, C, R)) {
-    const int bv = umamd::igemm_border_valu();
-    if (!((bv == 2 || (bv == 1 && K <= 8)) && C % 8 == 0 && K % 8 == 0)) {
-      umamd::IgArgs a{};
-      a.oh = H; a.ow = W; a.fold_pad = pad;
-      const long mb = (long)N * umamd::igemm_border_list(a);
-      // after the main pass's own workspace (its plan stays as sized by base)
-      return base + umamd::igemm_border_ws_bytes(dtype, (int)mb, C, R * R, K);
-    }
-  }
-  return base;
-}
-
-int um_conv_stats_parts(int M, int K) {
-  return ceil_div(M, umamd::igemm_stats_rows(M, K));
-}
-
-long um_conv_fwd_ws(int dtype, int N, int P, int Q, int K, int R, int C) {
-  return umamd::igemm_ws_bytes(dtype, N * P * Q, K, R * R, C);
-}
-
-long um_conv_dgrad_ws(int dtype, int N, int H, int W, int C, int R, int K, int stride) {
+// split-K workspace bytes of a data gradient (the zero-pad / one-pass form)
+long conv_dgrad_ws(int dtype, int N, int H, int W, int C, int R, int K, int stride) {
   if (stride == 1) return umamd::igemm_ws_bytes(dtype, N * H * W, C, R * R, K);
   long b = 0;  // the largest parity class (the launches reuse one workspace)
   const int taps = ((R + 1) / 2) * ((R + 1) / 2);
@@ -997,6 +963,42 @@ long um_conv_dgrad_ws(int dtype, int N, int H, int W, int C, int R, int K, int s
     b = std::max(b, umamd::igemm_cls4_ws_bytes(dtype, M, tp, C, K));
   }
   return b;
+}
+
+}  // namespace
+
+extern "C" {
+
+long um_conv_dgrad_ws_pad(int dtype, int N, int H, int W, int C, int R, int K, int stride, int pad,
+                          int pad_mode) {
+  const long base = conv_dgrad_ws(dtype, N, H, W, C, R, K, stride);
+  if (pad_dgrad_applies(dtype, N, C, R, pad, pad_mode, stride, H, W, H, W))
+    return std::max(base, pad_dgrad_bytes(dtype, N, H, W, C, R, K, pad, nullptr));
+  // split form of a reflect data gradient: the border-list GEMM of the fold
+  // splits its k-loop too (a few thousand rows x 9 taps: unsplit, 96-256
+  // workgroups ran 24-53 us behind a 30-87 us main pass), unless the fold is
+  // the VALU pass (um_conv2d_dgrad)
+  const int border_split = umamd::knobs().border_split;
+  if (border_split && pad_mode == UM_PAD_REFLECT && pad > 0 && stride == 1 &&
+      split_form(dtype, N, H, W, C, R)) {
+    const int bv = umamd::knobs().border_valu;
+    if (!((bv == 2 || (bv == 1 && K <= 8)) && C % 8 == 0 && K % 8 == 0)) {
+      umamd::IgArgs a{};
+      a.oh = H; a.ow = W; a.fold_pad = pad;
+      const long mb = (long)N * umamd::igemm_border_list(a);
+      // after the main pass's own workspace (its plan stays as sized by base)
+      return base + umamd::igemm_border_ws_bytes(dtype, (int)mb, C, R * R, K);
+    }
+  }
+  return base;
+}
+
+int um_conv_stats_parts(int M, int K) {
+  return ceil_div(M, umamd::igemm_stats_rows(M, K));
+}
+
+long um_conv_fwd_ws(int dtype, int N, int P, int Q, int K, int R, int C) {
+  return umamd::igemm_ws_bytes(dtype, N * P * Q, K, R * R, C);
 }
 
 static int conv2d_fwd(int dtype, int N, int H, int W, int C, int ldx, const void* x,
@@ -1180,7 +1182,7 @@ int um_conv2d_fwd_up2(int dtype, int N, int H, int W, int C, int ldx, const void
                "um_conv2d_fwd_up2: epilogue");
   UM_CHECK_ARG(K % 8 == 0 && ldy % 8 == 0 && up2_ld % 8 == 0 && P == H && Q == W,
                "um_conv2d_fwd_up2: K / strides must be multiples of 8, 1x1 same-size conv");
-  static const int valu = (int)umamd::tuning_env("up2_valu", 1);
+  const int valu = umamd::knobs().up2_valu;
   const int G = K / 8;
   if (valu && C % 8 == 0 && C <= 16 && K <= 128 && 256 % G == 0 && ldx % 8 == 0 &&
       (epilogue == UM_EPI_NONE || epilogue == UM_EPI_STAT_SLOTS)) {
@@ -1298,7 +1300,7 @@ int um_conv2d_dgrad(int dtype, int N, int H, int W, int C, int ldx, void* dx, in
     // the (zero-pad) transposed conv over every pixel (all fast paths apply) ...
     // (its workspace: the first `base` bytes; the border GEMM's split
     // partials follow them, um_conv_dgrad_ws_pad)
-    const long base = um_conv_dgrad_ws(dtype, N, H, W, C, R, K, stride);
+    const long base = conv_dgrad_ws(dtype, N, H, W, C, R, K, stride);
     int rc = umamd::igemm_run(dtype, a, (float*)ws, ws ? std::min(ws_bytes, base) : 0, st);
     if (rc != UM_OK || fold1 || pad_mode != UM_PAD_REFLECT || pad == 0) return rc;
     // ... then the reflect fold: the pixels rows/columns 1..pad and H-1-pad..H-2
@@ -1313,7 +1315,7 @@ int um_conv2d_dgrad(int dtype, int N, int H, int W, int C, int ldx, void* dx, in
     // (tools/border_micro.sh r04aa): 256x512 C32 K8 80.9 -> 77.2 us, 128x256
     // C64 K8 59.5 -> 55.5; at K = 32 / 64 the GEMM stays ahead (144 vs 163,
     // 59 vs 83 us).  Knob border_valu: 0 never, 1 K <= 8, 2 always
-    const int bv = umamd::igemm_border_valu();
+    const int bv = umamd::knobs().border_valu;
     if ((bv == 2 || (bv == 1 && K <= 8)) && C % 8 == 0 && K % 8 == 0 && ldx % 8 == 0 && a.M > 0) {
       const long threads = (long)a.M * (C / 8);
       if (dtype == UM_BF16)
@@ -1385,8 +1387,8 @@ static int generic_wgrad_splits(int M, int K, int RRC, bool tr) {
   const long tiles = (long)ceil_div(K, bm) * ceil_div(RRC, 128);
   // target workgroups over the chip: for the transposed-read kernel ONE round
   // of resident workgroups (occupancy x CUs; 768 was 1.5 rounds of the
-  // 2-per-CU instance), else 768 (UMAMD_TUNING wsplit_blocks for sweeps)
-  static const long fixed = umamd::tuning_env("wsplit_blocks", 0);
+  // 2-per-CU instance), else 768 (tuning key wsplit_blocks > 0 fixes it)
+  const long fixed = umamd::knobs().wsplit_blocks;
   const long target = fixed > 0 ? fixed
                       : tr      ? (long)umamd::wgrad_tr_blocks_per_cu(K) * cu_count()
                                 : 768;
@@ -1486,7 +1488,7 @@ int um_conv_wgrad_reduce_seg(const float* slabs, int splits, int K, int Kreal, i
   UM_CHECK_ARG(make_segs(g, nseg, src0, dst0, len, Creal, C), "um_conv_wgrad_reduce: segments");
   const long total = (long)Kreal * R * R * C;
   const long RRC = (long)R * R * C;
-  static const int wred_t = (int)umamd::tuning_env("wred_t", 1);
+  const int wred_t = umamd::knobs().wred_t;
   if (wred_t && R > 1 && total >= (1l << 18)) {
     const size_t shm = (size_t)R * R * (WRT_CW + 1) * sizeof(float);
     hipLaunchKernelGGL(wgrad_reduce_t_kernel, dim3(ceil_div(C, WRT_CW), Kreal), dim3(256), shm, st,
@@ -1515,12 +1517,6 @@ int um_conv_wgrad_reduce_seg(const float* slabs, int splits, int K, int Kreal, i
                      R, C, Creal, dw, accumulate, g, L);
   UM_LAUNCH_CHECK();
   return UM_OK;
-}
-
-int um_conv_wgrad_reduce(const float* slabs, int splits, int K, int Kreal, int R, int C,
-                         int Creal, float* dw, int accumulate, hipStream_t st) {
-  return um_conv_wgrad_reduce_seg(slabs, splits, K, Kreal, R, C, Creal, dw, accumulate, 0,
-                                  nullptr, nullptr, nullptr, st);
 }
 
 int um_pack_weight_seg(int dtype, const float* w, int K, int Creal, int R, int C, void* wf,

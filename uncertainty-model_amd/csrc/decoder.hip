@@ -14,6 +14,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "knobs.h"
 
 namespace {
 
@@ -797,10 +798,7 @@ __global__ void __launch_bounds__(256) parts_accum_kernel(const float* __restric
 // Measured slower (decoder concats 514 -> 693 us per step, 716 -> 705
 // pairs/s): waves spanning several sources run every source's path, and the
 // per-source launches already write whole 16-byte lanes
-bool cat_fused() {
-  static const int v = (int)umamd::tuning_env("cat_fused", 0);
-  return v != 0;
-}
+bool cat_fused() { return umamd::knobs().cat_fused != 0; }
 
 }  // namespace
 

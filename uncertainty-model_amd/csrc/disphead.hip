@@ -33,6 +33,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "knobs.h"
 
 namespace {
 
@@ -604,8 +605,7 @@ int um_disp_head_fwd(int N, int H, int W, int C, const void* x, int ldx, const v
   // loads; 21.3 -> 12.1 us over the k-split strips at C = 128), the k-split
   // strip kernel for C = 256 (16k pixels).  dh_fwd = 1: the shift-load column
   // kernel; dh_fwd128 = 0: the k-split strips at C = 128
-  static const int var = (int)umamd::tuning_env("dh_fwd", 0);
-  static const int var128 = (int)umamd::tuning_env("dh_fwd128", 1);
+  const int var = umamd::knobs().dh_fwd, var128 = umamd::knobs().dh_fwd128;
   auto col_units = [&](int U) { return N * ((H + U - 1) / U) * (W / 16); };
   switch (C) {
     case 32:
@@ -661,7 +661,7 @@ int um_disp_head_dgrad(int N, int H, int W, int C, const void* dl, int ldl, cons
   }
   // measured: LDS-staged 16-byte rows (STG) 36.8 -> 23.6 us (C = 32, U = 8) and
   // 21.2 -> 12.1 us (C = 64, U = 4) over 8-byte stores; dh_dgrad = 0: unstaged
-  static const int var = (int)umamd::tuning_env("dh_dgrad", 1);
+  const int var = umamd::knobs().dh_dgrad;
   switch (C) {
     case 32:
       if (var == 0) UM_DHC(2, 8, false) else UM_DHC(2, 8, true)

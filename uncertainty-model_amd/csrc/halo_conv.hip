@@ -31,6 +31,7 @@
 
 #include "common.h"
 #include "halo_conv.h"
+#include "knobs.h"
 
 namespace {
 
@@ -459,7 +460,7 @@ __global__ void __launch_bounds__(256) halo_conv_kernel(IgArgs a, int tiles_x, i
 // or (tests) at most knob halo_grid
 template <typename K>
 int persist_grid(K kernel, int ntiles, int col_blocks, size_t shm) {
-  const int mult = umamd::igemm_halo_persist(), cap = umamd::igemm_halo_grid();
+  const int mult = umamd::knobs().halo_persist, cap = umamd::knobs().halo_grid;
   if (cap > 0) return std::max(1, std::min(ntiles, cap));
   if (mult <= 0) return ntiles;
   static int cus = 0;
@@ -483,8 +484,8 @@ int persist_grid(K kernel, int ntiles, int col_blocks, size_t shm) {
 // 8x256x512 C32->K32 fwd 74.5 -> 66.5 us, dgrad 75.1 -> 65.9; a two-chunk
 // layer (C48 -> K32, reflect) went 94 -> 106 us forward, so it streams.
 size_t res_bytes(const IgArgs& a, int bn) {
-  const int kb = umamd::igemm_halo_res_kb();
-  if (kb <= 0 || a.R != 3 || a.ach > CK || umamd::igemm_halo_pf2()) return 0;
+  const int kb = umamd::knobs().halo_res_kb;
+  if (kb <= 0 || a.R != 3 || a.ach > CK || umamd::knobs().halo_pf2) return 0;
   const size_t b = (size_t)9 * bn * CK * sizeof(bf16_t);
   return b <= (size_t)kb * 1024 ? b : 0;
 }
@@ -520,7 +521,7 @@ int launch_r(const IgArgs& a, hipStream_t st) {
     }
   }
   if constexpr (BN <= 32 || (R == 3 && BN <= 64)) {
-    if (umamd::igemm_halo_pf2()) launch_rp<R, BN, 1>(a, ncb, tiles_x, tiles_y, 0, st);
+    if (umamd::knobs().halo_pf2) launch_rp<R, BN, 1>(a, ncb, tiles_x, tiles_y, 0, st);
     else launch_rp<R, BN, 0>(a, ncb, tiles_x, tiles_y, 0, st);
   } else {
     launch_rp<R, BN, 0>(a, ncb, tiles_x, tiles_y, 0, st);
@@ -583,7 +584,7 @@ bool halo_applicable(int dtype, const IgArgs& a, int min_tiles, int max_nc) {
 
 int halo_run(const IgArgs& a0, hipStream_t st) {
   IgArgs a = a0;
-  a.staged = igemm_halo_staged();
+  a.staged = knobs().halo_staged;
   if (a.R == 3) return launch_bn<3>(a, st);
   if (a.R == 5) return launch_bn<5>(a, st);
   return launch_bn<7>(a, st);

@@ -88,28 +88,9 @@ int igemm_run_cls4(int dtype, IgArgs (&as)[4], float* ws, long ws_bytes, hipStre
 // workspace of the 4-class LDS-DMA form (0 when it does not apply or needs none)
 long igemm_cls4_ws_bytes(int dtype, const int (&M)[4], const int (&taps)[4], int NC, int ach);
 
-// reflect data gradients with more input channels than this run as one fold
-// pass, the others as a zero-pad pass + the border-list pass (knob
-// "fold_split_nc")
-int igemm_fold_split_nc();
+// the zero-pad pass of a reflect data gradient in split form would run on
+// the halo kernel
 bool igemm_halo_dgrad(int dtype, int N, int H, int W, int C, int R);
-
-// reflect data gradients in the padded form (knob pad_dgrad): 0 off, 1 for
-// dx wider than fold_split_nc, 2 all
-int igemm_pad_dgrad();
-
-// halo conv weight rows two rows ahead (tuning key "halo_pf2")
-int igemm_halo_pf2();
-// halo conv grid: persistent workgroups per resident slot (knob
-// "halo_persist", 0 = one tile per workgroup) and a grid cap ("halo_grid")
-int igemm_halo_persist();
-int igemm_halo_grid();
-// resident-weight LDS budget (KB) of the 3x3 halo convs ("halo_res_kb", 0 = off)
-int igemm_halo_res_kb();
-// halo conv bf16 outputs staged through LDS as 16-byte rows ("halo_staged")
-int igemm_halo_staged();
-// reflect fold of the split-form data gradient as a VALU pass ("border_valu")
-int igemm_border_valu();
 
 // fill the border-list fields of a (oh, ow, fold_pad set) and return the
 // number of listed pixels per image

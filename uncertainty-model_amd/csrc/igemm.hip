@@ -32,11 +32,14 @@
 #include "common.h"
 #include "igemm.h"
 #include "halo_conv.h"
+#include "knobs.h"
 #include "stream1x1.h"
 
 namespace {
 
 using umamd::IgArgs;
+using umamd::Knobs;
+using umamd::knobs;
 
 // BN partial-statistics row block (um_conv_stats_parts): a.stats_rows, 128 or
 // 64 (the 64x64-tile plans); BM is a multiple of it.
@@ -1019,111 +1022,6 @@ struct Plan {
   int bk, bm, bn, wm, wn, splits, steps, per;
 };
 
-// tuning knobs (read once; defaults below, UMAMD_TUNING="key=value,..." for
-// sweeps, um_set_tuning at run time for tests)
-struct Knobs {
-  int small, small_tiles, split_below, split_target, split_minsteps, halo, halo_min_tiles, odd_bn, bk64;
-  int glds_split_below, glds_split_target;
-  int glds;
-  int glds_deep, glds_deep_blocks;
-  int xcd_col;
-  int tappack;
-  int cls4;
-  int cls_glds;
-  int pad_dgrad;
-  int fold_split_nc;
-  int halo_max_nc;
-  int halo_pf2;
-  int halo_persist, halo_grid, halo_res_kb;
-  int halo_staged;
-  int border_valu;
-  int s1x1, s1x1_small;
-  Knobs() {
-    auto env = [](const char* n, int d) { return (int)umamd::tuning_env(n, d); };
-    small = env("small", 1);
-    // measured on MI355X (bench step, tools/sweep.sh): the deep layers' main
-    // loops are load-latency bound (one double-buffered stage in flight per
-    // block, ~1 us per k-step at 1 block per CU), so more, smaller and split
-    // tiles help: 160/320/8/256 -> 600/1024/4/1024 took 578 -> 599 pairs/s
-    small_tiles = env("small_tiles", 1024);
-    split_below = env("split_below", 600);
-    split_target = env("split_target", 1024);
-    // the 8-wave LDS-DMA loop (glds bit 2) hides more of a 64x64-tile
-    // block's own latency: measured per conv (tools/ig_micro.sh), split only
-    // below 256 tiles and to ~512 blocks -- 16x32x256->256 27 -> 24 us,
-    // 32x64x128->128 27 -> 19 us, 8x16x512->512 28 -> 25 us.  The register
-    // path (reflect-fold data gradients, f32) keeps the thresholds above.
-    glds_split_below = env("glds_split_below", 256);
-    glds_split_target = env("glds_split_target", 512);
-    split_minsteps = env("split_minsteps", 4);
-    halo = env("halo", 1);
-    halo_min_tiles = env("halo_min_tiles", 256);
-    // widest output (columns) the halo kernel takes: 64 = one column block
-    // (round 2); up to 192 adds 96/128-wide 3x3 blocks and column grids
-    halo_max_nc = env("halo_max_nc", 192);
-    odd_bn = env("odd_bn", 1);
-    // bit 0: 64-deep k-steps for the 64x64 tiles, bit 1: for the 128-row tiles
-    bk64 = env("bk64", 3);
-    // bit 0: LDS-DMA main loop for the 64x64 tiles, bit 1: for the 128-row
-    // tiles, bit 2: 8 waves per 64x64 tile.  Step sweep (tools/sweep.sh):
-    // 0 -> 653.6, 7 -> 654.8, 5 -> 661.3 pairs/s (the 128-row tiles keep the
-    // register path: 3 LDS stages of 128-row tiles leave 1 block per CU)
-    glds = env("glds", 5);
-    // 6-stage LDS-DMA loop for 8-wave 64x64 grids of at most this many
-    // blocks (one 96 KB block per CU); 3 = off.  Step sweep: 3 -> 721,
-    // 6 -> 715 pairs/s (unsplit deep grids 713-717): five k-steps in flight
-    // do not shorten the deep layers' k-loop, so latency is not its limit
-    glds_deep = env("glds_deep", 3);
-    glds_deep_blocks = env("glds_deep_blocks", 256);
-    // column-major tile order for weight-heavy GEMMs (0 off, 1 auto, 2 on):
-    // per conv and per step within noise (714 vs 713 pairs/s), off
-    xcd_col = env("xcd_col", 0);
-    // 8-channel operands: bit 0 packs 4 taps per 32-deep k-step, bit 1 also
-    // routes them past the halo kernel.  First conv (7x7 s2, C8) 93 -> 51 us;
-    // step 711 -> 715-716 pairs/s with 1 or 3 (the heads' halo path is as fast)
-    tappack = env("tappack", 1);
-    // the four parity classes of a stride-2 data gradient as one launch
-    cls4 = env("cls4", 1);
-    // the four parity classes of a stride-2 data gradient as one launch of
-    // LDS-DMA tiles instead of 256-row register tiles (bit 0: NC a multiple
-    // of 64 on 64x64 tiles: 64x128 C64 K128 59 -> 28 us, 32x64 C128 K256
-    // 50 -> 24, 16x32 C256 K512 57 -> 28; bit 1: NC = 32 on 64x32 tiles with
-    // 4 waves: 128x256 C32 K64 5x5 79 -> 63 us; MI355X, tools/gpu_s2_micro.sh)
-    cls_glds = env("cls_glds", 3);
-    // reflect data gradient as a zero-pad transposed conv onto the padded
-    // input + a fold pass (0 off, 1 the wide layers, 2 all)
-    pad_dgrad = env("pad_dgrad", 1);
-    // per conv (tools/conv_table.py): split form 256x512 C48 171 -> 117 us,
-    // C32 K8 125 -> 85; one pass stays ahead from C = 128 up (16x32 C640:
-    // 106 vs 140, 8x16 C512: 53 vs 79)
-    fold_split_nc = env("fold_split_nc", 64);
-    // halo conv: weight tap rows loaded two rows ahead (halo_conv.hip PF2)
-    halo_pf2 = env("halo_pf2", 0);
-    // halo conv as persistent workgroups (resident count x this; 0 = one
-    // tile per workgroup) that prefetch the next tile's halo; halo_grid > 0
-    // caps the grid (tests: several tiles per workgroup on small images)
-    halo_persist = env("halo_persist", 1);
-    halo_grid = env("halo_grid", 0);
-    // 3x3 halo convs keep all their tap weights in LDS (per workgroup, for
-    // all its tiles) when they need at most this many KB; 0 = stream rows
-    halo_res_kb = env("halo_res_kb", 48);
-    // halo conv bf16 outputs through LDS as 16-byte rows (halo_conv.hip)
-    halo_staged = env("halo_staged", 1);
-    // reflect fold of the split-form data gradient: a VALU pass over the
-    // border list (conv.hip reflect_border_kernel) instead of the GEMM
-    border_valu = env("border_valu", 1);
-    // high-resolution 1x1 convs (M >= 16k, C <= 256, N <= 192) on the
-    // streaming kernel (stream1x1.hip) instead of 256-row GEMM tiles
-    s1x1 = env("s1x1", 1);
-    // small-M 1x1 convs (stream1x1.hip s1x1_small_kernel, M < 16k pixels)
-    s1x1_small = env("s1x1_small", 1);
-  }
-};
-Knobs& knobs() {
-  static Knobs k;
-  return k;
-}
-
 // Deep layers (few 128x128 tiles) use 64x64 tiles: 4x the workgroups, more of
 // them per CU (32 KB of LDS each), so more loads in flight per CU instead of
 // a split-K round trip through an f32 workspace.  Depends on (M, NC) only so
@@ -1286,8 +1184,6 @@ int dispatch_tiles(const IgArgs& a, const Plan& p, float* ws, hipStream_t st) {
 
 namespace umamd {
 
-int igemm_fold_split_nc() { return knobs().fold_split_nc; }
-
 // the zero-pad pass of a reflect data gradient in split form would run on
 // the halo kernel ("same" 3x3/5x5/7x7, 8x32 tiles, enough of them)
 bool igemm_halo_dgrad(int dtype, int N, int H, int W, int C, int R) {
@@ -1296,13 +1192,6 @@ bool igemm_halo_dgrad(int dtype, int N, int H, int W, int C, int R) {
   if (H % 8 || W % 32 || C > k.halo_max_nc || C % 8) return false;
   return (long)N * (H / 8) * (W / 32) >= k.halo_min_tiles;
 }
-int igemm_pad_dgrad() { return knobs().pad_dgrad; }
-int igemm_halo_pf2() { return knobs().halo_pf2; }
-int igemm_halo_persist() { return knobs().halo_persist; }
-int igemm_halo_grid() { return knobs().halo_grid; }
-int igemm_halo_res_kb() { return knobs().halo_res_kb; }
-int igemm_halo_staged() { return knobs().halo_staged; }
-int igemm_border_valu() { return knobs().border_valu; }
 
 int igemm_border_list(IgArgs& a) {
   const int H = a.oh, W = a.ow, p = a.fold_pad;
@@ -1536,43 +1425,3 @@ int igemm_run_cls4(int dtype, IgArgs (&as)[4], float* ws, long ws_bytes, hipStre
 }
 
 }  // namespace umamd
-
-// tuning knobs at run time (tests force code paths; sweeps): returns the old
-// value, or -1 for an unknown key
-extern "C" int um_set_tuning(const char* key, int value) {
-  Knobs& k = knobs();
-  int* f = nullptr;
-  if (!strcmp(key, "halo")) f = &k.halo;
-  else if (!strcmp(key, "halo_min_tiles")) f = &k.halo_min_tiles;
-  else if (!strcmp(key, "small")) f = &k.small;
-  else if (!strcmp(key, "small_tiles")) f = &k.small_tiles;
-  else if (!strcmp(key, "split_below")) f = &k.split_below;
-  else if (!strcmp(key, "split_target")) f = &k.split_target;
-  else if (!strcmp(key, "glds_split_below")) f = &k.glds_split_below;
-  else if (!strcmp(key, "glds_split_target")) f = &k.glds_split_target;
-  else if (!strcmp(key, "split_minsteps")) f = &k.split_minsteps;
-  else if (!strcmp(key, "odd_bn")) f = &k.odd_bn;
-  else if (!strcmp(key, "bk64")) f = &k.bk64;
-  else if (!strcmp(key, "glds")) f = &k.glds;
-  else if (!strcmp(key, "glds_deep")) f = &k.glds_deep;
-  else if (!strcmp(key, "xcd_col")) f = &k.xcd_col;
-  else if (!strcmp(key, "tappack")) f = &k.tappack;
-  else if (!strcmp(key, "cls4")) f = &k.cls4;
-  else if (!strcmp(key, "cls_glds")) f = &k.cls_glds;
-  else if (!strcmp(key, "pad_dgrad")) f = &k.pad_dgrad;
-  else if (!strcmp(key, "glds_deep_blocks")) f = &k.glds_deep_blocks;
-  else if (!strcmp(key, "fold_split_nc")) f = &k.fold_split_nc;
-  else if (!strcmp(key, "halo_max_nc")) f = &k.halo_max_nc;
-  else if (!strcmp(key, "halo_pf2")) f = &k.halo_pf2;
-  else if (!strcmp(key, "halo_persist")) f = &k.halo_persist;
-  else if (!strcmp(key, "halo_grid")) f = &k.halo_grid;
-  else if (!strcmp(key, "halo_res_kb")) f = &k.halo_res_kb;
-  else if (!strcmp(key, "halo_staged")) f = &k.halo_staged;
-  else if (!strcmp(key, "border_valu")) f = &k.border_valu;
-  else if (!strcmp(key, "s1x1")) f = &k.s1x1;
-  else if (!strcmp(key, "s1x1_small")) f = &k.s1x1_small;
-  if (!f) return -1;
-  const int old = *f;
-  *f = value;
-  return old;
-}

@@ -6,10 +6,10 @@
 //       sigmoid(w[widx[i]]) where the host passes the reference's index map
 //       (F3: widx = [0, 0, 1, 2, ...]).
 //   um_image_to_nhwc   NCHW f32 image -> NHWC (padded channels, zero fill)
-//   um_axpy            y += alpha * x over n elements (gradient accumulation)
 //   um_sigmoid_scale_bwd  d/dlogit of scale*sigmoid(logit) (disp head,
 //       reference model/layers/decoder.py:246 with ConvLayer sigmoid)
 #include "common.h"
+#include "knobs.h"
 
 namespace {
 
@@ -353,13 +353,6 @@ __global__ void image_to_nhwc8_kernel(const float* __restrict__ x, int N, int C,
   }
 }
 
-template <typename T>
-__global__ void axpy_kernel(long n, float alpha, const T* __restrict__ x, T* __restrict__ y) {
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n;
-       i += (long)gridDim.x * blockDim.x)
-    y[i] = from_f32<T>(to_f32(y[i]) + alpha * to_f32(x[i]));
-}
-
 // dlogit[m][c] = dd[m][c] * d * (1 - d/scale) for c < C (SPLIT: also at
 // C + c, the split-bf16 head's residual rows); the other channels of [0, ldo)
 // zeroed
@@ -507,7 +500,7 @@ int um_merge_bwd_bn(int dtype, int nsrc, const void* const* srcs, void* const* d
   const long n8 = count / 8, M = count / C;
   // sources 2-4 on the loads-first instances (tuning key merge_ns = 0: the
   // runtime source loop for all)
-  static const int ns_on = (int)umamd::tuning_env("merge_ns", 1);
+  const int ns_on = umamd::knobs().merge_ns;
   const int ns = ns_on && nsrc >= 2 && nsrc <= 4 ? nsrc : 0;
 #define UM_MBB_NS(T_, TY_, NS_)                                                                   \
   hipLaunchKernelGGL((merge_bwd_bn_kernel<T_, TY_, NS_>), dim3(merge_bn_grid(n8)), dim3(256), 0, st, a,  \
@@ -570,17 +563,6 @@ int um_image_to_nhwc(int dtype, const float* x, int N, int C, int H, int W, int 
   else
     hipLaunchKernelGGL(image_to_nhwc_kernel<float>, dim3(grid_for(total)), dim3(256), 0, st, x, N,
                        C, H, W, Cp, (float*)out);
-  UM_LAUNCH_CHECK();
-  return UM_OK;
-}
-
-int um_axpy(int dtype, long n, float alpha, const void* x, void* y, hipStream_t st) {
-  if (dtype == UM_BF16)
-    hipLaunchKernelGGL(axpy_kernel<bf16_t>, dim3(grid_for(n)), dim3(256), 0, st, n, alpha,
-                       (const bf16_t*)x, (bf16_t*)y);
-  else
-    hipLaunchKernelGGL(axpy_kernel<float>, dim3(grid_for(n)), dim3(256), 0, st, n, alpha,
-                       (const float*)x, (float*)y);
   UM_LAUNCH_CHECK();
   return UM_OK;
 }

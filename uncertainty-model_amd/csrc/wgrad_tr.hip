@@ -24,6 +24,7 @@
 
 #include "common.h"
 #include "wgrad_tr.h"
+#include "knobs.h"
 
 namespace {
 
@@ -293,13 +294,10 @@ namespace umamd {
 
 int wgrad_tr_bm(int K) { return K <= 64 ? 64 : 128; }
 
-// pixels per k-step (tuning key wtr_tbk: 32, 64 or 128)
+// pixels per k-step (tuning key wtr_tbk: 64 or 128, anything else means 32)
 int wgrad_tr_tbk() {
-  static const int v = [] {
-    const int t = (int)umamd::tuning_env("wtr_tbk", 32);
-    return (t == 64 || t == 128) ? t : 32;
-  }();
-  return v;
+  const int t = knobs().wtr_tbk;
+  return (t == 64 || t == 128) ? t : 32;
 }
 
 // resident 256-thread workgroups per CU of the instance wgrad_tr_run picks for K

@@ -5,6 +5,7 @@ is present, ``lib()`` raises.  Every wrapper passes torch's *current* stream.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 from typing import Optional
@@ -66,12 +67,10 @@ _SIG = {
     'um_conv2d_fwd_up2': (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _I, _I, _P,
                                _P, _I, _I, _I, 's']),
     'um_conv_fwd_ws': (_L, [_I, _I, _I, _I, _I, _I, _I]),
-    'um_conv_dgrad_ws': (_L, [_I, _I, _I, _I, _I, _I, _I, _I]),
     'um_conv_dgrad_ws_pad': (_L, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I]),
     'um_conv_wgrad_splits': (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I]),
     'um_conv2d_wgrad': (_I, [_I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I,
                              _P, _I, 's']),
-    'um_conv_wgrad_reduce': (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _I, 's']),
     'um_pack_weight': (_I, [_I, _P, _I, _I, _I, _I, _P, _P, _I, 's']),
     'um_pack_batch': (_I, [_I, _P, _I, _P, _I, 's']),
     'um_pack_desc_size': (_I, []),
@@ -89,7 +88,6 @@ _SIG = {
     'um_bn_bwd_stats_coeffs': (_I, [_P, _I, _I, _P, _D, _P, _P, _P, _P, _P, _P, _P, _P, 's']),
     'um_bn_coeffs': (_I, [_P, _D, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _P, 's']),
     'um_bn_fold': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _F, _P, _P, 's']),
-    'um_bn_fwd_pool_parts': (_I, [_L, _L]),
     'um_bn_fwd_pool_parts_c': (_I, [_L, _L, _I]),
     'um_bn_elu_fwd': (_I, [_I, _L, _I, _P, _I, _P, _P, _P, _I, _I, _L, _P, 's']),
     'um_bn_elu_fwd_slots': (_I, [_I, _L, _I, _P, _I, _P, _D, _P, _P, _F, _F, _P, _P, _P, _P, _P,
@@ -116,7 +114,6 @@ _SIG = {
     'um_merge_wgrad': (_I, [_P, _I, _I, _P, _P, _P, _I, _I, 's']),
     'um_merge_wgrad_batch': (_I, [_P, _I, 's']),
     'um_image_to_nhwc': (_I, [_I, _P, _I, _I, _I, _I, _I, _P, 's']),
-    'um_axpy': (_I, [_I, _L, _F, _P, _P, 's']),
     'um_sigmoid_scale_bwd': (_I, [_I, _L, _I, _P, _I, _P, _I, _F, _P, _I, 's']),
     'um_sigmoid_scale_bwd_split': (_I, [_I, _L, _I, _P, _I, _P, _I, _F, _P, _I, 's']),
     'um_head_split_fin': (_I, [_L, _I, _P, _I, _P, _F, _P, _I, 's']),
@@ -172,7 +169,6 @@ _SIG = {
     'um_stereo_prep': (_I, [_I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P,
                             's']),
     'um_adam_chunk': (_I, []),
-    'um_adam_step': (_I, [_P, _P, _I, _F, _F, _F, _F, _F, _I, 's']),
     'um_adam_step_dev': (_I, [_P, _P, _I, _F, _P, _F, _F, _F, _F, _P, 's']),
 }
 
@@ -282,6 +278,24 @@ def call(name: str, *args, work=None):
 def query(name: str, *args):
     """Call a pure host-side query entry (no stream)."""
     return getattr(lib(), name)(*args)
+
+
+@contextlib.contextmanager
+def tuning(**knobs):
+    """Set tuning keys (csrc/knobs.h) for the duration of a block and put the
+    old values back on exit, also when the block raises.  An unknown key
+    raises UmamdError (and restores what was set before it)."""
+    old = {}
+    try:
+        for k, v in knobs.items():
+            prev = lib().um_set_tuning(k.encode(), int(v))
+            if prev == -1:
+                raise UmamdError(f'unknown tuning key {k!r}')
+            old[k] = prev
+        yield
+    finally:
+        for k, v in old.items():
+            lib().um_set_tuning(k.encode(), v)
 
 
 def require_device(t: torch.Tensor):
