@@ -555,6 +555,34 @@ int um_spars_sort(const float* keys, const float* vals, int nseg, int L, float* 
 int um_spars_curve(const float* sorted_vals, int nseg, int L, int steps, double* ws,
                    float* curve, hipStream_t stream);
 
+/* The fused per-batch form of the above for the captured evaluation engine
+ * (umamd/evalengine.py).  acc is the engine's f64 accumulator block
+ * {left SSIM sum, right SSIM sum, AUSE sum, AURG sum, batch count}
+ * (the running_* sums of reference train/evaluate.py:160-176). */
+/* Both views of one batch in one launch + a finish launch, replacing
+ * reconstruct_left/right_image, the two SSIM calls and image_error of
+ * evaluate.py:137-151.  left/right [N][3][H][W]; pred NHWC f32, element
+ * (n, y, x, ch) at pred[n*pred_sn + (y*W + x)*pred_sp + ch], channels 0/1 the
+ * disparities (the strides of um_warp).  recon [N][6][H][W] or NULL (not
+ * written); err [N][2][H][W] = WeightedSSIMLoss(alpha=1).image_error;
+ * acc[0] / acc[1] += the view's gaussian SSIM (11 taps, sigma 1.5, data range
+ * 1) summed over the batch (reduction='sum').  H, W >= 12; ws: um_eval_ws()
+ * bytes */
+long um_eval_ws(int N, int H, int W);
+int um_eval_maps(const float* left, const float* right, const float* pred, long pred_sn,
+                 long pred_sp, int N, int H, int W, float* recon, float* err, double* ws,
+                 double* acc, hipStream_t stream);
+/* nn.AvgPool2d(11, stride=1) (sparsification.py:14-16) of err [N][2][H][W],
+ * of channels 2/3 of pred (strides as above) and of rnd [N][2][H][W], each
+ * written as sort-ready segments [2N][(H-10)*(W-10)].  Only k = 11. */
+int um_eval_pool(const float* err, const float* pred, long pred_sn, long pred_sp,
+                 const float* rnd, int N, int H, int W, int k, float* err_out, float* unc_out,
+                 float* rnd_out, hipStream_t stream);
+/* acc[2] += ause = sum(pred - oracle)/steps, acc[3] += aurg = sum(random -
+ * pred)/steps (sparsification.py:43-61), acc[4] += 1 */
+int um_eval_accum(const float* oracle_curve, const float* pred_curve, const float* random_curve,
+                  int steps, double* acc, hipStream_t stream);
+
 /* ---------------------------------------------------------------- adam ---
  * torch.optim.Adam step, reference train/train.py:228-229.
  */

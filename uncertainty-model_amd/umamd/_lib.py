@@ -165,6 +165,10 @@ _SIG = {
     'um_spars_sort_ws': (_L, [_I, _I]),
     'um_spars_sort': (_I, [_P, _P, _I, _I, _P, _P, _P, _L, 's']),
     'um_spars_curve': (_I, [_P, _I, _I, _I, _P, _P, 's']),
+    'um_eval_ws': (_L, [_I, _I, _I]),
+    'um_eval_maps': (_I, [_P, _P, _P, _L, _L, _I, _I, _I, _P, _P, _P, _P, 's']),
+    'um_eval_pool': (_I, [_P, _P, _L, _L, _P, _I, _I, _I, _I, _P, _P, _P, 's']),
+    'um_eval_accum': (_I, [_P, _P, _P, _I, _P, 's']),
     'um_stereo_prep_ws': (_L, [_I, _I, _I]),
     'um_stereo_prep': (_I, [_I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P,
                             's']),
