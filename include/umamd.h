@@ -111,6 +111,16 @@ int um_conv2d_dgrad(int dtype, int N, int H, int W, int C, int ldx, void* dx,
                     int accumulate, const void* wT, int K, int R, int stride,
                     int pad, int pad_mode, int P, int Q, const void* dy, int ldy,
                     void* ws, long ws_bytes, hipStream_t stream);
+/* 1 when um_conv2d_fwd (dgrad 0) or the main pass of um_conv2d_dgrad (dgrad 1:
+ * x is [N][H][W][C], dy [N][P][Q][K], with the workspace of
+ * um_conv_dgrad_ws_pad) would run on the halo-tiled kernel (csrc/halo_conv.hip)
+ * under the current tuning keys, else 0.  Dense operands (ldx = C, ldy = K);
+ * the dispatch itself decides, so this cannot drift from it.  Host only: needs
+ * no device.  The halo kernel does not take partial-row statistics
+ * (UM_EPI_STATS) unless P % 8 == 0 and Q % 32 == 0, nor reflect padding where
+ * a tile's halo would need a second reflection. */
+int um_conv_halo_ok(int dtype, int N, int H, int W, int C, int K, int R, int stride, int pad,
+                    int pad_mode, int P, int Q, int epilogue, int dgrad);
 
 /* weight gradient partial slabs [splits][K][R*R*C] (f32); splits from
  * um_conv_wgrad_splits (which also picks the kernel: the halo-tiled one for

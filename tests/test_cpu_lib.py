@@ -153,6 +153,117 @@ def test_tuning_keys_take_effect_at_run_time():
         assert query(*q) == dflt, q
 
 
+def _halo_ok(N, H, W, C, K, R, mode, epi, dgrad=0):
+    """um_conv_halo_ok of a stride-1 "same" bf16 conv (the dispatch's own
+    answer under the current tuning keys)"""
+    from umamd import _lib as L
+    return L.query('um_conv_halo_ok', L.UM_BF16, N, H, W, C, K, R, 1, (R - 1) // 2,
+                   L.PAD_REFLECT if mode == 'reflect' else L.PAD_ZERO, H, W, epi, dgrad)
+
+
+def test_halo_dispatch_rules():
+    """the two shapes of problem the halo kernel must not take: partial-row
+    statistics on a ragged tiling (two rows per tile overrun the
+    um_conv_stats_parts rows) and reflect padding where a tile's halo would
+    reflect twice (load_halo reflects once: an index before the tensor)"""
+    from umamd import _lib as L
+    from umamd._lib import tuning
+    with tuning(halo_min_tiles=1):
+        for (P, Q), want in (((16, 32), 1), ((10, 32), 0), ((12, 20), 0), ((8, 40), 0)):
+            assert _halo_ok(2, P, Q, 32, 32, 3, 'zero', L.EPI_STATS) == want, (P, Q)
+            assert _halo_ok(2, P, Q, 32, 32, 3, 'zero', L.EPI_STAT_SLOTS) == 1, (P, Q)
+            assert _halo_ok(2, P, Q, 32, 32, 3, 'zero', L.EPI_NONE) == 1, (P, Q)
+        for (H, W), want in (((9, 17), 1), ((13, 33), 1), ((8, 32), 1), ((8, 16), 0), ((4, 32), 0)):
+            assert _halo_ok(2, H, W, 32, 32, 3, 'reflect', L.EPI_NONE) == want, (H, W)
+            assert _halo_ok(2, H, W, 32, 32, 3, 'zero', L.EPI_NONE) == 1, (H, W)  # zero pad: masked
+        assert _halo_ok(2, 8, 33, 32, 32, 5, 'reflect', L.EPI_NONE) == 0
+        assert _halo_ok(2, 8, 34, 32, 32, 5, 'reflect', L.EPI_NONE) == 1
+        # the rest of the predicate igemm_run applies, seen through the query
+        assert _halo_ok(2, 16, 32, 8, 32, 3, 'zero', L.EPI_NONE) == 1
+        with tuning(tappack=3):  # 8-channel operands: the tap-packed GEMM first
+            assert _halo_ok(2, 16, 32, 8, 32, 3, 'zero', L.EPI_NONE) == 0
+        with tuning(halo=0):
+            assert _halo_ok(2, 16, 32, 32, 32, 3, 'zero', L.EPI_NONE) == 0
+        assert _halo_ok(2, 16, 32, 32, 32, 3, 'zero', L.EPI_NONE, dgrad=1) == 1
+        assert L.query('um_conv_halo_ok', L.UM_F32, 2, 16, 32, 32, 32, 3, 1, 1, L.PAD_ZERO, 16, 32,
+                       L.EPI_NONE, 0) == 0
+        assert L.query('um_conv_halo_ok', L.UM_BF16, 2, 16, 32, 32, 32, 3, 2, 1, L.PAD_ZERO, 8, 16,
+                       L.EPI_NONE, 0) == 0  # stride 2
+    assert _halo_ok(2, 16, 32, 32, 32, 3, 'zero', L.EPI_NONE) == 0  # 4 tiles < halo_min_tiles
+
+
+# The stride-1 3x3/5x5/7x7 convs of the configured model (config.yml) at
+# 256x512, batch 8: (H, W, Cin padded to 8, Cout, R, pad mode, on the halo
+# kernel under default keys).  Encoder: model/layers/encoder.py NodeBlock, the
+# non-input nodes of stages 1-3 (the input nodes are stride 2); decoder:
+# model/layers/decoder.py DecoderStage.upsample (at the stage input's size,
+# 4 * upsample_channels outputs) and .iconv (upsample + skip_out + disparity
+# channels) of stages 3-5.  Stage 3 and the upsample conv of decoder stage 3
+# run at 32x64: 64 tiles, below halo_min_tiles.
+MODEL_HALO_SHAPES = [
+    (128, 256, 32, 32, 7, 'zero', 1),     # encoder stage 1 nodes
+    (64, 128, 64, 64, 5, 'zero', 1),      # encoder stage 2 nodes
+    (32, 64, 128, 128, 3, 'zero', 0),     # encoder stage 3 nodes
+    (32, 64, 256, 128, 3, 'reflect', 0),  # decoder stage 3 upsample
+    (64, 128, 168, 128, 3, 'reflect', 1),  # decoder stage 3 iconv (32 + 128 + 4)
+    (64, 128, 128, 64, 3, 'reflect', 1),  # decoder stage 4 upsample
+    (128, 256, 88, 64, 3, 'reflect', 1),  # decoder stage 4 iconv (16 + 64 + 4)
+    (128, 256, 64, 32, 3, 'reflect', 1),  # decoder stage 5 upsample
+    (256, 512, 48, 32, 3, 'reflect', 1),  # decoder stage 5 iconv (8 + 32 + 4)
+]
+
+
+def test_halo_takes_the_model_shapes():
+    """under default keys the model's high-resolution convs stay on the halo
+    kernel, forward (training statistics in slots or partial rows, and the
+    inference ELU form) and the zero-pad data gradient: none of them is a
+    ragged tiling or needs a second reflection, so the two refusals of
+    test_halo_dispatch_rules change nothing for them"""
+    import _halo_cases as HC
+    from umamd import _lib as L
+    for H, W, C, K, R, mode, want in MODEL_HALO_SHAPES:
+        assert H % HC.TH == 0 and W % HC.TW == 0
+        assert not HC.reflect_needs_second(R, H, W)
+        for epi in (L.EPI_STAT_SLOTS, L.EPI_ELU, L.EPI_NONE):
+            assert _halo_ok(8, H, W, C, K, R, mode, epi) == want, (H, W, C, K, R, mode, epi)
+        # partial rows (the step outside a stat_scope): not where the GEMM's
+        # 64-row tiles set the row layout (more than 64 channels, few tiles)
+        rows128 = L.query('um_conv_stats_parts', 8 * H * W, K) == 8 * H * W // 128
+        assert _halo_ok(8, H, W, C, K, R, mode, L.EPI_STATS) == (want if rows128 else 0)
+        if mode == 'zero':
+            assert _halo_ok(8, H, W, C, K, R, mode, L.EPI_NONE, dgrad=1) == want, (H, W, C, K, R)
+
+
+def test_halo_test_guard_sizes():
+    """the guarded statistics buffers of tests/test_gpu_halo_conv.py hold the
+    rows of either kernel -- two per 8 x 32 tile (the halo kernel, with or
+    without the exact-tiling condition) or um_conv_stats_parts (the GEMM) --
+    plus sentinel rows, for every ragged and every refused case; and the
+    Python copy of the reflect condition agrees with the library"""
+    import _halo_cases as HC
+    from umamd import _lib as L
+    from umamd._lib import tuning
+    for case in HC.RAGGED_CASES + HC.REFUSED_CASES:
+        C, K, R, mode, H, W = case
+        tiles2 = 2 * HC.N * -(-H // 8) * -(-W // 32)
+        parts = L.query('um_conv_stats_parts', HC.N * H * W, K)
+        assert HC.stat_buffer_rows(H, W, parts) >= max(tiles2, parts) + 2, case
+        assert HC.halo_stat_rows(H, W) == tiles2
+    # the ragged tilings are the ones where the two counts differ
+    assert all(2 * HC.N * -(-c[4] // 8) * -(-c[5] // 32) >
+               L.query('um_conv_stats_parts', HC.N * c[4] * c[5], c[1]) for c in HC.RAGGED_CASES)
+    with tuning(halo_min_tiles=1):
+        for case in HC.EXACT_CASES + HC.RAGGED_CASES + HC.REFUSED_CASES + HC.EPILOGUE_CASES:
+            C, K, R, mode, H, W = case
+            second = mode == 'reflect' and HC.reflect_needs_second(R, H, W)
+            assert _halo_ok(HC.N, H, W, C, K, R, mode, L.EPI_NONE) == (0 if second else 1), case
+            assert second == (case in HC.REFUSED_CASES), case
+    # reflect inputs: the slack covers the R - 1 rows and columns a halo reaches
+    for C, K, R, mode, H, W in HC.RAGGED_CASES + HC.REFUSED_CASES:
+        assert HC.reflect_slack(C, R, W) >= (R - 1) * (W + 1) * C
+        assert HC.reflect_slack(C, R, W) % 8 == 0
+
+
 def test_kernel_call_fails_loudly_on_cpu_tensor():
     import torch
     from umamd import functional as U

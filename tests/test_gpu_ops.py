@@ -53,8 +53,11 @@ CONV_CASES = [
 
 
 # shapes the halo-tiled direct conv takes (bf16, stride 1, "same" padding,
-# P % 8 == 0, Q % 32 == 0, K <= 64); the tile-count threshold is lowered so
-# these small images use it (forward + zero-pad data gradient)
+# Q >= 16, K <= halo_max_nc); the tile-count threshold is lowered so these
+# small images use it (forward + zero-pad data gradient).  These are exact
+# 8 x 32 tilings -- the kernel masks partial edge tiles, and only refuses
+# them for partial-row statistics (two rows per tile) -- the ragged ones and
+# the kernel against f64 references are in test_gpu_halo_conv.py
 HALO_CASES = [
     (32, 32, 7, 1, 'zero', 16, 32),
     (64, 64, 5, 1, 'zero', 8, 64),

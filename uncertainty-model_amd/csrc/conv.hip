@@ -965,6 +965,62 @@ long conv_dgrad_ws(int dtype, int N, int H, int W, int C, int R, int K, int stri
   return b;
 }
 
+// The problems the C entries hand to igemm_run, without their pointers and
+// output fields: everything the host-side dispatch reads.  The entries and the
+// um_conv_halo_ok query build them here, so the query sees what runs.
+umamd::IgArgs fwd_problem(int N, int H, int W, int C, int ldx, int K, int R, int stride, int pad,
+                          int pad_mode, int P, int Q, int epilogue) {
+  umamd::IgArgs a{};
+  a.ah = H; a.aw = W; a.ach = C; a.lda = ldx;
+  a.on = N; a.oh = P; a.ow = Q;
+  a.R = R; a.stride = stride; a.pad = pad;
+  a.Rx = R; a.padx = pad; a.tsign = 1; a.wR = R;
+  a.pmode = pad_mode == UM_PAD_REFLECT ? umamd::IG_PAD_REFLECT : umamd::IG_PAD_ZERO;
+  a.fold_pad = 0; a.flip = 0;
+  a.ldb = (long)R * R * C;
+  a.NC = K; a.M = N * P * Q;
+  a.epilogue = epilogue == UM_EPI_STAT_SLOTS ? UM_EPI_STATS : epilogue;
+  a.stat_slots = epilogue == UM_EPI_STAT_SLOTS;
+  return a;
+}
+
+// stride-1 data gradient, padded form: the zero-pad transposed conv onto the
+// (H+2p) x (W+2p) padded input
+umamd::IgArgs dgrad_padded_problem(int N, int H, int W, int C, int K, int R, int pad, int P, int Q,
+                                   int ldy) {
+  const int Hp = H + 2 * pad, Wp = W + 2 * pad;
+  umamd::IgArgs a{};
+  a.ah = P; a.aw = Q; a.ach = K; a.lda = ldy;
+  a.on = N; a.oh = Hp; a.ow = Wp;
+  a.R = R; a.stride = 1; a.pad = R - 1;
+  a.Rx = R; a.padx = R - 1; a.tsign = 1; a.wR = R;
+  a.pmode = umamd::IG_PAD_ZERO; a.fold_pad = 0; a.flip = 1;
+  a.ldb = (long)R * R * K;
+  a.NC = C; a.M = N * Hp * Wp;
+  a.epilogue = UM_EPI_NONE;
+  return a;
+}
+
+// stride-1 data gradient, the transposed conv over every dx pixel
+umamd::IgArgs dgrad_problem(int dtype, int N, int H, int W, int C, int K, int R, int pad,
+                            int pad_mode, int P, int Q, int ldy) {
+  umamd::IgArgs a{};
+  a.ah = P; a.aw = Q; a.ach = K; a.lda = ldy;
+  a.on = N; a.oh = H; a.ow = W;
+  a.R = R; a.stride = 1; a.pad = R - 1 - pad;
+  a.Rx = R; a.padx = R - 1 - pad; a.tsign = 1; a.wR = R;
+  // reflect pad, split form (narrow dx: the zero-pad pass takes the halo /
+  // 256-row tiles, 117 vs 171 us at 256x512 C48) or one fold pass (wide dx:
+  // the deep layers' border list is 18-34 % of their pixels)
+  const bool fold1 = pad_mode == UM_PAD_REFLECT && pad > 0 && !split_form(dtype, N, H, W, C, R);
+  a.pmode = fold1 ? umamd::IG_FOLD : umamd::IG_PAD_ZERO;
+  a.fold_pad = fold1 ? pad : 0; a.flip = 1;
+  a.ldb = (long)R * R * K;
+  a.NC = C; a.M = N * H * W;
+  a.epilogue = UM_EPI_NONE;
+  return a;
+}
+
 }  // namespace
 
 extern "C" {
@@ -995,6 +1051,20 @@ long um_conv_dgrad_ws_pad(int dtype, int N, int H, int W, int C, int R, int K, i
 
 int um_conv_stats_parts(int M, int K) {
   return ceil_div(M, umamd::igemm_stats_rows(M, K));
+}
+
+int um_conv_halo_ok(int dtype, int N, int H, int W, int C, int K, int R, int stride, int pad,
+                    int pad_mode, int P, int Q, int epilogue, int dgrad) {
+  if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0 || P <= 0 || Q <= 0) return 0;
+  if (!dgrad)
+    return umamd::igemm_takes_halo(
+        dtype, fwd_problem(N, H, W, C, C, K, R, stride, pad, pad_mode, P, Q, epilogue));
+  // the main pass of um_conv2d_dgrad (stride 2 runs as parity classes)
+  if (stride != 1 || epilogue != UM_EPI_NONE) return 0;
+  if (pad_dgrad_applies(dtype, N, C, R, pad, pad_mode, stride, P, Q, H, W))
+    return umamd::igemm_takes_halo(dtype, dgrad_padded_problem(N, H, W, C, K, R, pad, P, Q, K));
+  return umamd::igemm_takes_halo(dtype,
+                                 dgrad_problem(dtype, N, H, W, C, K, R, pad, pad_mode, P, Q, K));
 }
 
 long um_conv_fwd_ws(int dtype, int N, int P, int Q, int K, int R, int C) {
@@ -1225,18 +1295,9 @@ static int conv2d_fwd(int dtype, int N, int H, int W, int C, int ldx, const void
   UM_CHECK_ARG(epilogue != UM_EPI_ELU || (!accumulate && stats == nullptr),
                "um_conv2d_fwd: UM_EPI_ELU takes no statistics and does not accumulate");
   UM_CHECK_ARG(ydtype == dtype || ydtype == UM_F32, "um_conv2d_fwd: ydtype must be dtype or f32");
-  umamd::IgArgs a{};
-  a.a = x; a.ah = H; a.aw = W; a.ach = C; a.lda = ldx;
-  a.on = N; a.oh = P; a.ow = Q;
-  a.R = R; a.stride = stride; a.pad = pad;
-  a.Rx = R; a.padx = pad; a.tsign = 1; a.wR = R;
-  a.pmode = pad_mode == UM_PAD_REFLECT ? umamd::IG_PAD_REFLECT : umamd::IG_PAD_ZERO;
-  a.fold_pad = 0; a.flip = 0;
-  a.b = wf; a.ldb = (long)R * R * C;
-  a.NC = K; a.M = N * P * Q;
+  umamd::IgArgs a = fwd_problem(N, H, W, C, ldx, K, R, stride, pad, pad_mode, P, Q, epilogue);
+  a.a = x; a.b = wf;
   a.bias = bias; a.out = y; a.ld_out = ldy; a.out_f32 = (ydtype == UM_F32);
-  a.epilogue = epilogue == UM_EPI_STAT_SLOTS ? UM_EPI_STATS : epilogue;
-  a.stat_slots = epilogue == UM_EPI_STAT_SLOTS;
   a.accumulate = accumulate; a.epi_scale = epi_scale;
   a.residual = residual; a.ldr = ldr; a.stats = stats;
   return umamd::igemm_run(dtype, a, (float*)ws, ws_bytes, st);
@@ -1257,17 +1318,10 @@ int um_conv2d_dgrad(int dtype, int N, int H, int W, int C, int ldx, void* dx, in
         ws_bytes >= pad_dgrad_bytes(dtype, N, H, W, C, R, K, pad, &goff)) {
       // padded form: zero-pad transposed conv onto the (H+2p) x (W+2p) padded
       // input (halo / LDS-DMA / register GEMM paths), then the reflect fold
-      const int Hp = H + 2 * pad, Wp = W + 2 * pad;
-      umamd::IgArgs a{};
-      a.a = dy; a.ah = P; a.aw = Q; a.ach = K; a.lda = ldy;
-      a.on = N; a.oh = Hp; a.ow = Wp;
-      a.R = R; a.stride = 1; a.pad = R - 1;
-      a.Rx = R; a.padx = R - 1; a.tsign = 1; a.wR = R;
-      a.pmode = umamd::IG_PAD_ZERO; a.fold_pad = 0; a.flip = 1;
-      a.b = wT; a.ldb = (long)R * R * K;
-      a.NC = C; a.M = N * Hp * Wp;
+      umamd::IgArgs a = dgrad_padded_problem(N, H, W, C, K, R, pad, P, Q, ldy);
+      a.a = dy; a.b = wT;
       a.bias = nullptr; a.out = ws; a.ld_out = C; a.out_f32 = (dtype == UM_F32);
-      a.epilogue = UM_EPI_NONE; a.accumulate = 0; a.epi_scale = 1.f;
+      a.accumulate = 0; a.epi_scale = 1.f;
       a.residual = nullptr; a.ldr = 0; a.stats = nullptr;
       int rc = umamd::igemm_run(dtype, a, reinterpret_cast<float*>((char*)ws + goff), ws_bytes - goff, st);
       if (rc != UM_OK) return rc;
@@ -1281,21 +1335,11 @@ int um_conv2d_dgrad(int dtype, int N, int H, int W, int C, int ldx, void* dx, in
       UM_LAUNCH_CHECK();
       return UM_OK;
     }
-    umamd::IgArgs a{};
-    a.a = dy; a.ah = P; a.aw = Q; a.ach = K; a.lda = ldy;
-    a.on = N; a.oh = H; a.ow = W;
-    a.R = R; a.stride = 1; a.pad = R - 1 - pad;
-    a.Rx = R; a.padx = R - 1 - pad; a.tsign = 1; a.wR = R;
-    // reflect pad, split form (narrow dx: the zero-pad pass takes the halo /
-    // 256-row tiles, 117 vs 171 us at 256x512 C48) or one fold pass (wide dx:
-    // the deep layers' border list is 18-34 % of their pixels)
-    const bool fold1 = pad_mode == UM_PAD_REFLECT && pad > 0 && !split_form(dtype, N, H, W, C, R);
-    a.pmode = fold1 ? umamd::IG_FOLD : umamd::IG_PAD_ZERO;
-    a.fold_pad = fold1 ? pad : 0; a.flip = 1;
-    a.b = wT; a.ldb = (long)R * R * K;
-    a.NC = C; a.M = N * H * W;
+    umamd::IgArgs a = dgrad_problem(dtype, N, H, W, C, K, R, pad, pad_mode, P, Q, ldy);
+    const bool fold1 = a.pmode == umamd::IG_FOLD;
+    a.a = dy; a.b = wT;
     a.bias = nullptr; a.out = dx; a.ld_out = ldx; a.out_f32 = (dtype == UM_F32);
-    a.epilogue = UM_EPI_NONE; a.accumulate = accumulate; a.epi_scale = 1.f;
+    a.accumulate = accumulate; a.epi_scale = 1.f;
     a.residual = nullptr; a.ldr = 0; a.stats = nullptr;
     // the (zero-pad) transposed conv over every pixel (all fast paths apply) ...
     // (its workspace: the first `base` bytes; the border GEMM's split

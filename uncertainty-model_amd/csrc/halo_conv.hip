@@ -23,6 +23,9 @@
 // Epilogue as igemm's: bias, optional residual / sigmoid-scale / accumulate,
 // f32 or bf16 output, and the BN partial statistics (two 128-pixel rows per
 // tile, so um_conv_stats_parts counts them like the GEMM's).
+// Not taken (halo_applicable): partial-row statistics on a ragged tiling
+// (oh % 8 or ow % 32), and reflect where a tile's halo would need a second
+// reflection (last tile origin + tile - 1 + pad > 2 * (n - 1), rows or columns).
 // Replaces nn.Conv2d forward / input-gradient of reference
 // model/layers/encoder.py:36-42 (7x7, 5x5, 3x3 zero padded) and
 // model/layers/decoder.py:30-52 (3x3 reflection padded, forward).
@@ -575,9 +578,20 @@ bool halo_applicable(int dtype, const IgArgs& a, int min_tiles, int max_nc) {
   // 64-column block the tap-packed GEMM is faster (disp-head data gradient
   // 64x128 C128 K8: 35 us tap-packed vs 49 us on 128-wide halo blocks)
   if (a.ach < 32 && a.NC > 64) return false;
-  // partial-row statistics follow the GEMM's 128-row layout; the f64 slots
+  // partial-row statistics follow the GEMM's 128-row layout: two rows per
+  // tile are the um_conv_stats_parts rows only when the 8 x 32 tiling is
+  // exact (a ragged one writes 2 * tiles > ceil(M / 128) rows); the f64 slots
   // (stat_slots) take any tiling
-  if (a.epilogue == UM_EPI_STATS && !a.stat_slots && a.stats_rows != 128) return false;
+  if (a.epilogue == UM_EPI_STATS && !a.stat_slots &&
+      (a.stats_rows != 128 || a.oh % TH != 0 || a.ow % TW != 0))
+    return false;
+  // load_halo reflects an index once: the last tile's halo reaches row
+  // t0 + TH - 1 + pad (t0 its origin; the columns likewise with TW), which
+  // one reflection maps into the image only up to 2 * (n - 1)
+  if (a.pmode == IG_PAD_REFLECT &&
+      ((a.oh - 1) / TH * TH + TH - 1 + a.pad > 2 * (a.ah - 1) ||
+       (a.ow - 1) / TW * TW + TW - 1 + a.pad > 2 * (a.aw - 1)))
+    return false;
   // enough tiles to fill the chip
   return (long)a.on * ((a.oh + TH - 1) / TH) * ((a.ow + TW - 1) / TW) >= min_tiles;
 }

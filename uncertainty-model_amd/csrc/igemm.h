@@ -81,6 +81,9 @@ long igemm_ws_bytes(int dtype, int M, int NC, int taps, int ach);
 long igemm_border_ws_bytes(int dtype, int M, int NC, int taps, int ach);
 // launch; ws may be null (then no split)
 int igemm_run(int dtype, const IgArgs& a, float* ws, long ws_bytes, hipStream_t st);
+// igemm_run would hand this problem to the halo kernel (halo_conv.hip) under
+// the current tuning keys; host only, launches nothing
+bool igemm_takes_halo(int dtype, const IgArgs& a);
 
 // the four parity classes of a stride-2 data gradient in one launch: 1 =
 // launched, 0 = not eligible (launch them one by one), < 0 = -error code

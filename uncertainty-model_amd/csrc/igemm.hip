@@ -1222,9 +1222,14 @@ long igemm_border_ws_bytes(int dtype, int M, int NC, int taps, int ach) {
 
 int igemm_stats_rows(int M, int NC) { return small_tiles(M, NC) ? 64 : 128; }
 
-int igemm_run(int dtype, const IgArgs& a_in, float* ws, long ws_bytes, hipStream_t st) {
-  if (a_in.M == 0) return UM_OK;
-  IgArgs a = a_in;
+// Which kernel family igemm_run hands a problem to, decided on the host from
+// the problem and the tuning keys alone; also sets the fields igemm_run owns
+// (stats_rows, colmajor).  igemm_run and the um_conv_halo_ok query both go
+// through it, so the query cannot drift from the dispatch.
+enum Route { ROUTE_NONE, ROUTE_BORDER, ROUTE_S1X1, ROUTE_S1X1_SMALL, ROUTE_HALO, ROUTE_GEMM };
+
+static Route igemm_route(int dtype, IgArgs& a) {
+  if (a.M == 0) return ROUTE_NONE;
   a.stats_rows = igemm_stats_rows(a.M, a.NC);
   {
     // column-major tile order when B (NC x taps x ach) is larger than the
@@ -1233,7 +1238,28 @@ int igemm_run(int dtype, const IgArgs& a_in, float* ws, long ws_bytes, hipStream
     const long abytes = (long)a.M * a.ach, bbytes = (long)a.NC * a.R * a.Rx * a.ach;
     a.colmajor = xc == 2 || (xc == 1 && bbytes > abytes);
   }
-  if (a.border) {
+  if (a.border) return ROUTE_BORDER;
+  if (knobs().s1x1 && stream1x1_applicable(dtype, a)) return ROUTE_S1X1;
+  if (knobs().s1x1_small && s1x1_small_applicable(dtype, a)) return ROUTE_S1X1_SMALL;
+  // 8-channel operands take the tap-packed GEMM instead of the halo kernel
+  // (which stages 32-channel chunks) unless tappack bit 1 is clear
+  const bool pack_first = (knobs().tappack & 3) == 3 && a.ach == 8;
+  if (knobs().halo && !pack_first &&
+      halo_applicable(dtype, a, knobs().halo_min_tiles, knobs().halo_max_nc))
+    return ROUTE_HALO;
+  return ROUTE_GEMM;
+}
+
+bool igemm_takes_halo(int dtype, const IgArgs& a_in) {
+  IgArgs a = a_in;
+  return igemm_route(dtype, a) == ROUTE_HALO;
+}
+
+int igemm_run(int dtype, const IgArgs& a_in, float* ws, long ws_bytes, hipStream_t st) {
+  IgArgs a = a_in;
+  const Route route = igemm_route(dtype, a);
+  if (route == ROUTE_NONE) return UM_OK;
+  if (route == ROUTE_BORDER) {
     // the reflect fold's border list: a few thousand rows, one small plan
     Plan p{};
     p.bk = 32; p.bm = 64; p.bn = 64; p.wm = 2; p.wn = 2;
@@ -1242,14 +1268,9 @@ int igemm_run(int dtype, const IgArgs& a_in, float* ws, long ws_bytes, hipStream
     if (dtype == UM_BF16) return launch_cls<bf16_t, 32, 64, 64, 2, 2, 2>(a, p, ws, st);
     return launch_cls<float, 32, 64, 64, 2, 2, 2>(a, p, ws, st);
   }
-  if (knobs().s1x1 && stream1x1_applicable(dtype, a)) return stream1x1_run(a, st);
-  if (knobs().s1x1_small && s1x1_small_applicable(dtype, a)) return s1x1_small_run(a, st);
-  // 8-channel operands take the tap-packed GEMM instead of the halo kernel
-  // (which stages 32-channel chunks) unless tappack bit 1 is clear
-  const bool pack_first = (knobs().tappack & 3) == 3 && a.ach == 8;
-  if (knobs().halo && !pack_first &&
-      halo_applicable(dtype, a, knobs().halo_min_tiles, knobs().halo_max_nc))
-    return halo_run(a, st);
+  if (route == ROUTE_S1X1) return stream1x1_run(a, st);
+  if (route == ROUTE_S1X1_SMALL) return s1x1_small_run(a, st);
+  if (route == ROUTE_HALO) return halo_run(a, st);
   // the LDS-DMA loop serves the bf16 64x64 tiles without the reflect fold
   Plan p = make_plan(dtype, a.M, a.NC, a.R * a.Rx, a.ach, ws ? ws_bytes : 0, false);
   if (dtype == UM_BF16 && p.bm == 64 && p.bk == 64 && a.pmode != IG_FOLD && (knobs().glds & 1))

@@ -66,6 +66,7 @@ _SIG = {
                              _P, _I, _P, _L, 's']),
     'um_conv2d_fwd_up2': (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _I, _I, _P,
                                _P, _I, _I, _I, 's']),
+    'um_conv_halo_ok': (_I, [_I] * 14),
     'um_conv_fwd_ws': (_L, [_I, _I, _I, _I, _I, _I, _I]),
     'um_conv_dgrad_ws_pad': (_L, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I]),
     'um_conv_wgrad_splits': (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I]),
