@@ -621,6 +621,54 @@ int um_stereo_prep(int N, int Hs, int Ws, const unsigned char* left,
                    const float* params, unsigned char* tmp, float* out_left, float* out_right,
                    hipStream_t stream);
 
+/* ---------------------------------------------------------- deployment ---
+ * A camera frame to metric depth around the inference engine
+ * (umamd/deploy.py DepthPipeline: um_frame_prep -> forward -> um_depth_post
+ * as one captured graph).
+ */
+/* ResizeImage -> ToTensor (reference train/transforms.py:15-41) of one view
+ * in ONE launch: src uint8 [N][Hs][Ws][3] -> out f32 [N][3][Hd][Wd], written
+ * into the caller's buffer.  Tables and integer arithmetic of um_stereo_prep
+ * (22-bit fixed point, round half up, clip to [0, 255] after each pass, then
+ * / 255.0f): bit-identical to PIL and to um_stereo_prep without flip or
+ * augment.  A workgroup owns 8 output rows x 32 output columns, runs the
+ * horizontal pass for the source rows its vertical taps need into LDS (u8)
+ * and the vertical pass out of LDS: no workspace, no 8-bit intermediate in
+ * memory.
+ * The limit (um_frame_prep_ok answers 0, um_frame_prep returns UM_ERR_ARG):
+ * ceil(7 * Hs / Hd) + 1 + ks_v source rows of a tile must fit 64 KiB of LDS
+ * at 128 bytes per row, i.e. be <= 512 (every upscale; a vertical downscale
+ * up to 56x), and ks_h <= 257 (a horizontal downscale up to 128x).  N <= 65535. */
+int um_frame_prep_ok(int Hs, int Ws, int Hd, int Wd, int ks_h, int ks_v);
+int um_frame_prep(int N, int Hs, int Ws, const unsigned char* src, int Hd, int Wd,
+                  const int* bounds_h, const int* kk_h, int ks_h, const int* bounds_v,
+                  const int* kk_v, int ks_v, float* out, hipStream_t stream);
+/* Everything after the forward, for the LEFT view at the frame's size
+ * (Hs, Ws), in one launch.  pred NHWC f32 with the strides of um_eval_maps
+ * (pred_sp >= 4), channels d_L, d_R, sigma_L, sigma_R at model size (H, W).
+ *   e           = |d_L - reconstruct_left_image(d_L, d_R)|: the left half of
+ *                 ConsistencyLoss (reference train/loss.py:179-185) with the
+ *                 warp of train/utils.py:65-103 (linspace(0, 1) grid,
+ *                 grid_sample bilinear / zeros / align_corners=False)
+ *   up(t)       = bilinear, align_corners=True, to (Hs, Ws) (the reference's
+ *                 map resize, loss.py:120-121, evaluate.py:152-153)
+ *   disparity   = up(d_L) * Ws      [source pixels]
+ *   lr_error    = up(e) * Ws        [source pixels]
+ *   uncertainty = up(sigma_L)
+ *   depth       = fb / disparity where disparity > min_disp_px, else 0
+ *   valid       = disparity > min_disp_px && uncertainty <= max_unc &&
+ *                 lr_error <= max_lr_px   (u8 0 / 1)
+ * The reference's only post-processing helper, train.utils.combine_disparity
+ * (utils.py:202-245), goes through numpy on the host and is not called; this
+ * is the device form of what follows its forward.  params: DEVICE f32[4] = (fb,
+ * min_disp_px, max_unc, max_lr_px), read by the kernel, so a captured graph
+ * sees new values at its next replay.  Outputs [N][Hs][Ws]; any of them may
+ * be NULL (skipped).  H, W, Hs, Ws >= 2; H, W <= 32768. */
+int um_depth_post(const float* pred, long pred_sn, long pred_sp, int N, int H, int W, int Hs,
+                  int Ws, const float* params, float* disparity, float* depth,
+                  float* uncertainty, float* lr_error, unsigned char* valid,
+                  hipStream_t stream);
+
 /* ------------------------------------------------ SyncBN exchange (IPC) ---
  * SyncBatchNorm statistics exchanged device-side over IPC-mapped per-rank
  * arenas instead of one RCCL all-reduce per layer and direction (reference

@@ -173,6 +173,9 @@ _SIG = {
     'um_stereo_prep_ws': (_L, [_I, _I, _I]),
     'um_stereo_prep': (_I, [_I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P,
                             's']),
+    'um_frame_prep_ok': (_I, [_I, _I, _I, _I, _I, _I]),
+    'um_frame_prep': (_I, [_I, _I, _I, _P, _I, _I, _P, _P, _I, _P, _P, _I, _P, 's']),
+    'um_depth_post': (_I, [_P, _L, _L, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, 's']),
     'um_adam_chunk': (_I, []),
     'um_adam_step_dev': (_I, [_P, _P, _I, _F, _P, _F, _F, _F, _F, _P, 's']),
 }

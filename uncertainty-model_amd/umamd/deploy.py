@@ -1,0 +1,186 @@
+"""Frame-to-depth pipeline: a uint8 camera frame in, metric depth with a
+confidence mask out, as one replayed HIP graph around the inference engine.
+
+``InferenceEngine`` maps a resized f32 [B,3,H,W] image to disparity (as a
+fraction of the width) and uncertainty at model resolution.  ``DepthPipeline``
+adds both ends of the deployment path,
+
+  um_frame_prep   uint8 [B,Hs,Ws,3] -> the engine's static f32 input
+                  (ResizeImage -> ToTensor, reference train/transforms.py:
+                  15-41: Pillow's bilinear resize, bit-exact, one launch)
+  -> forward      (umamd.infer.InferenceEngine: folded BatchNorm, packed weights)
+  -> um_depth_post  at the frame's size, left view: disparity in pixels,
+                  depth = focal x baseline / disparity, the upsampled
+                  uncertainty, the left-right consistency error and the
+                  validity mask (include/umamd.h "deployment")
+
+captured as ONE torch.cuda.CUDAGraph over static buffers.  ``__call__``
+copies the frames in and replays; it never synchronises with the host.  The
+calibration and the three thresholds live in a 4-float device block the kernel
+reads, so ``set_params`` needs no recapture.
+"""
+from __future__ import annotations
+
+import math
+
+import torch
+
+from . import _lib as L
+from ._lib import call, ptr, query
+from .imageprep import resize_coeffs
+from .infer import InferenceEngine, _eval_mode
+
+PARAMS = ('focal_baseline', 'min_disparity', 'max_uncertainty', 'max_lr_error')
+
+
+def _check_frames(frames, shape):
+    """a frame batch must be a uint8 tensor of exactly ``shape``"""
+    if not torch.is_tensor(frames) or frames.dtype != torch.uint8:
+        raise TypeError(f'DepthPipeline: uint8 frames expected, got '
+                        f'{frames.dtype if torch.is_tensor(frames) else type(frames)}')
+    if tuple(frames.shape) != tuple(shape):
+        raise ValueError(f'DepthPipeline built for frames {tuple(shape)} (uint8 [B, Hs, Ws, 3]), '
+                         f'got {tuple(frames.shape)}')
+
+
+class DepthPipeline:
+    """``pipe = DepthPipeline(model, src_height, src_width, batch=1, height=256,
+    width=512, scale=1.0, focal_baseline=1.0, min_disparity=1e-3,
+    max_uncertainty=inf, max_lr_error=inf)``; ``out = pipe(frames)`` with
+    ``frames`` uint8 [B,Hs,Ws,3] on the host (pinned or not) or the device.
+
+    ``out`` holds, for the left view at the frame's size ([B,Hs,Ws]):
+    ``disparity`` (source pixels), ``depth`` (``focal_baseline / disparity``
+    where ``disparity > min_disparity``, else 0; the unit of the baseline),
+    ``uncertainty`` (the model's sigma, upsampled), ``lr_error`` (left-right
+    consistency error, source pixels), ``valid`` (bool: ``disparity >
+    min_disparity and uncertainty <= max_uncertainty and lr_error <=
+    max_lr_error``), and ``prediction``, the engine's [B,4,H,W] output.
+
+    These are VIEWS OF THE PIPELINE'S STATIC BUFFERS: valid until the next
+    call (or refresh), which overwrites them -- clone what must outlive that.
+
+    ``focal_baseline`` is the focal length in source pixels times the
+    baseline; ``min_disparity`` and ``max_lr_error`` are in source pixels.
+    ``set_params`` changes any of the four without recapture.  ``refresh()``
+    must be called after the model's weights or running statistics changed.
+    ``fused`` is the InferenceEngine's switch; ``capture=False`` runs the same
+    three stages eagerly."""
+
+    def __init__(self, model, src_height: int, src_width: int, batch: int = 1, height: int = 256,
+                 width: int = 512, scale: float = 1.0, focal_baseline: float = 1.0,
+                 min_disparity: float = 1e-3, max_uncertainty: float = math.inf,
+                 max_lr_error: float = math.inf, fused: bool = True, capture: bool = True):
+        B, H, W, Hs, Ws = int(batch), int(height), int(width), int(src_height), int(src_width)
+        if H <= 0 or W <= 0 or H % 32 or W % 32:
+            raise ValueError(f'image size {H}x{W}: height and width must be multiples of 32')
+        if Hs < 2 or Ws < 2:
+            raise ValueError(f'source size {Hs}x{Ws}: height and width must be at least 2')
+        if B < 1:
+            raise ValueError(f'batch {B}')
+        bh, kh, ksh = resize_coeffs(Ws, W)
+        bv, kv, ksv = resize_coeffs(Hs, H)
+        if not query('um_frame_prep_ok', Hs, Ws, H, W, ksh, ksv):
+            raise ValueError(
+                f'source size {Hs}x{Ws} -> {H}x{W} is past the limit of um_frame_prep: every '
+                f'upscale, a vertical downscale up to 56x (ceil(7 * Hs / H) + 1 + ks_v <= 512 '
+                f'source rows of a tile in 64 KiB of LDS; here '
+                f'{-(-7 * Hs // H) + 1 + ksv}) and a horizontal one up to 128x (ks_h <= 257; '
+                f'here {ksh})')
+        self.infer = InferenceEngine(model, B, H, W, scale, fused=fused, capture=False)
+        self.model = self.infer.model
+        self.shape = (B, 3, H, W)
+        self.src_shape = (B, Hs, Ws, 3)
+        self.scale = float(scale)
+        self.capture = bool(capture)
+        dev = self.infer._in.device
+        self._frames = torch.zeros(self.src_shape, dtype=torch.uint8, device=dev)
+        self._tables = tuple(torch.from_numpy(a).to(dev) for a in (bh, kh, bv, kv))
+        self._ks = (ksh, ksv)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self._disparity = torch.zeros((B, Hs, Ws), **f32)
+        self._depth = torch.zeros((B, Hs, Ws), **f32)
+        self._uncertainty = torch.zeros((B, Hs, Ws), **f32)
+        self._lr_error = torch.zeros((B, Hs, Ws), **f32)
+        self._valid = torch.zeros((B, Hs, Ws), dtype=torch.uint8, device=dev)
+        self.params = {'focal_baseline': float(focal_baseline),
+                       'min_disparity': float(min_disparity),
+                       'max_uncertainty': float(max_uncertainty),
+                       'max_lr_error': float(max_lr_error)}
+        self._params = torch.tensor([self.params[k] for k in PARAMS], **f32)
+        self._graph = None
+        self._out = None
+        self._called = False
+        with torch.cuda.device(dev):
+            if self.capture:
+                self._capture()
+
+    # ---------------------------------------------------------------- runs --
+    def _run(self):
+        B, _, H, W = self.shape
+        _, Hs, Ws, _ = self.src_shape
+        bh, kh, bv, kv = self._tables
+        call('um_frame_prep', B, Hs, Ws, ptr(self._frames), H, W, ptr(bh), ptr(kh), self._ks[0],
+             ptr(bv), ptr(kv), self._ks[1], ptr(self.infer._in))
+        out = self.infer._forward()
+        if out.dtype != torch.float32 or out.stride(3) != 1 or out.stride(1) != W * out.stride(2):
+            raise L.UmamdError(f'DepthPipeline: prediction {out.dtype} with strides '
+                               f'{out.stride()} is not an NHWC f32 image')
+        call('um_depth_post', ptr(out), out.stride(0), out.stride(2), B, H, W, Hs, Ws,
+             ptr(self._params), ptr(self._disparity), ptr(self._depth), ptr(self._uncertainty),
+             ptr(self._lr_error), ptr(self._valid))
+        return out
+
+    def _capture(self):
+        cur = torch.cuda.current_stream()
+        side = torch.cuda.Stream()
+        side.wait_stream(cur)
+        with torch.no_grad(), _eval_mode(self.model):
+            with torch.cuda.stream(side):
+                self._run()  # warm-up (allocator, constants)
+            side.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=side):
+                out = self._run()
+        cur.wait_stream(side)
+        self._graph, self._out = g, out
+
+    def refresh(self):
+        """Re-fold and re-pack from the model's current weights and running
+        statistics (in place: the captured graph stays valid unless a
+        parameter's storage moved, which captures again)."""
+        before = self.infer._sites()
+        self.infer.refresh()
+        if self.capture and self.infer._sites() != before:
+            with torch.cuda.device(self._frames.device):
+                self._capture()
+
+    def set_params(self, **kw):
+        """any of focal_baseline, min_disparity, max_uncertainty, max_lr_error:
+        written into the device block in place, seen by the next call"""
+        bad = sorted(set(kw) - set(PARAMS))
+        if bad:
+            raise TypeError(f'DepthPipeline.set_params: unknown {bad}; one of {PARAMS}')
+        self.params.update({k: float(v) for k, v in kw.items()})
+        self._params.copy_(torch.tensor([self.params[k] for k in PARAMS], dtype=torch.float32))
+
+    def __call__(self, frames: torch.Tensor):
+        _check_frames(frames, self.src_shape)
+        self._frames.copy_(frames, non_blocking=True)
+        if self._graph is not None:
+            self._graph.replay()
+        else:
+            with torch.cuda.device(self._frames.device), torch.no_grad(), \
+                    _eval_mode(self.model):
+                self._out = self._run()
+        self._called = True
+        return self.last()
+
+    def last(self):
+        """views of the static buffers of the last call (valid until the next one)"""
+        if not self._called:
+            raise L.UmamdError('DepthPipeline.last() before the first call')
+        return {'disparity': self._disparity, 'depth': self._depth,
+                'uncertainty': self._uncertainty, 'lr_error': self._lr_error,
+                'valid': self._valid.view(torch.bool),
+                'prediction': self._out.permute(0, 3, 1, 2)[:, :4]}
