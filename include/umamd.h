@@ -499,6 +499,34 @@ int um_loss_bwd(int nscales, int N, int H, int W, const float* const* img,
                 float w_wssim, float w_cons, float w_smooth, float w_err,
                 const float* gout_disp, const float* gout_err, const float* const* gpart,
                 float* const* dpred, hipStream_t stream);
+/* The same loss with ReprojectionErrorLoss(pooling=True) (loss.py:405-434): at
+ * every scale the prediction, the image and the detached error map go through
+ * AvgPool2d(3, stride 1) ([h,w] -> [h-2,w-2]) before the error term (NLL,
+ * esw * smoothness, ecw * consistency) is evaluated; the last scale must be
+ * at least 4x4.  Arguments as um_loss_fwd / um_loss_bwd, except:
+ * emaps[s] [N][2][H>>s][W>>s] receives the unpooled error map of EVERY scale
+ * (emaps[nscales-1] is previous_image_error); pool_ws: um_loss_pool_ws() bytes,
+ * 16-byte aligned, caller-owned (no allocation, no host synchronisation).
+ * out[1] / out[5] / error_loss hold the pooled term; out[0], out[2..4] and
+ * disp_loss are what um_loss_fwd gives.  With gpart the forward also leaves
+ * the gradient w.r.t. the pooled maps in pool_ws: um_loss_pool_bwd with the
+ * same gpart and pool_ws is then two launches (the consistency scatter and
+ * the pool adjoint).  Without gpart the backward needs the forward's emaps
+ * and runs every stage itself; pool_ws is scratch.  The scatter into the
+ * sampled pooled disparity uses fixed-point integer atomics: the gradient
+ * does not depend on their order. */
+long um_loss_pool_ws(int nscales, int N, int H, int W);
+int um_loss_pool_fwd(int nscales, int N, int H, int W, const float* const* img,
+                     const float* const* pred, float alpha, int loss_type, float esw, float ecw,
+                     float w_wssim, float w_cons, float w_smooth, float w_err, double* ws,
+                     float* const* emaps, float* const* recon_out, float* out, float* disp_loss,
+                     float* error_loss, float* const* gpart, void* pool_ws, hipStream_t stream);
+int um_loss_pool_bwd(int nscales, int N, int H, int W, const float* const* img,
+                     const float* const* pred, float alpha, int loss_type, float esw, float ecw,
+                     float w_wssim, float w_cons, float w_smooth, float w_err,
+                     const float* gout_disp, const float* gout_err, const float* const* gpart,
+                     const float* const* emaps, void* pool_ws, float* const* dpred,
+                     hipStream_t stream);
 /* WeightedSSIMLoss.image_error (loss.py:96-131) of an explicit recon: out [N][2][H][W] */
 int um_image_error(const float* img, const float* rec, int N, int H, int W, float alpha,
                    float* out, hipStream_t stream);

@@ -342,7 +342,7 @@ struct LArgs {
   float esw, ecw;  // error-loss smoothness / consistency weights
   float w_wssim, w_cons, w_smooth, w_err;
   double* parts;      // fwd: [nblocks][8] f64 partial terms
-  float* emap;        // fwd: error map of the last scale [N][2][h][w] (or null)
+  float* emap[MAXS];  // fwd: error map of scale s [N][2][h][w] (or null; um_loss_fwd: the last)
   float* rec[MAXS];   // fwd (optional): the reconstruction [N][6][h][w] as a side output
   float* out;         // fwd: [6] disp_loss, error_loss, wssim, consistency, smoothness, error
   float* disp_loss;    // fwd (optional): out[0] again
@@ -692,6 +692,7 @@ __global__ void __launch_bounds__(FNT, 2) loss_fwd_kernel(LArgs a) {
   const int gh = H - 2, gw = W - 2;
   const float Wh = (float)W * 0.5f;
   float* const recp = pick(a.rec, s);
+  float* const emp = pick(a.emap, s);
   constexpr int KP = FTY * FTX / FNT;  // pixels per thread and view
   float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
@@ -755,8 +756,7 @@ __global__ void __launch_bounds__(FNT, 2) loss_fwd_kernel(LArgs a) {
       if (x == W - 1) gxi = 0.f;  // replicate-padded gradient (loss.py:208-218)
       if (y == H - 1) gyi = 0.f;
       const float ev = a.alpha * up + (1.f - a.alpha) * (l1 * (1.f / 3.f));
-      if (a.emap != nullptr && s == a.nscales - 1)
-        a.emap[(n * 2 + v) * HW + y * W + x] = ev;
+      if (emp != nullptr) emp[(n * 2 + v) * HW + y * W + x] = ev;
       if (recp != nullptr)
 #pragma unroll
         for (int c = 0; c < 3; ++c) recp[(n * 6 + v * 3 + c) * HW + y * W + x] = sR[c][rr][qq];
@@ -953,6 +953,7 @@ __global__ void __launch_bounds__(BNT, 2) loss_grad_kernel(LArgs a) {
   const float2 sav = FUSED ? make_float2(0.f, 0.f) : *reinterpret_cast<const float2*>(dslot);
   float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // FUSED: the forward's loss terms
   float* const recp = FUSED ? pick(a.rec, s) : nullptr;
+  float* const emp = FUSED ? pick(a.emap, s) : nullptr;
 
   stage_pred<BTY, BTX, BNT>(pp, H, W, ty0, tx0, sP);
   init_tabs<BTY, BTX>(tb, H, W, ty0, tx0);
@@ -1085,7 +1086,7 @@ __global__ void __launch_bounds__(BNT, 2) loss_grad_kernel(LArgs a) {
           if (a.loss_type == 1) acc[3] += fdiv(ev, sg) + __logf(sg);
           else if (a.loss_type == 2) acc[3] += fdiv(ev, __expf(-sg)) + sg;
           else acc[3] += fabsf(sg - ev);
-          if (a.emap != nullptr && s == a.nscales - 1) a.emap[(n * 2 + v) * HW + y * W + x] = ev;
+          if (emp != nullptr) emp[(n * 2 + v) * HW + y * W + x] = ev;
           if (recp != nullptr)
 #pragma unroll
             for (int c = 0; c < 3; ++c) recp[(n * 6 + v * 3 + c) * HW + y * W + x] = sR[c][rr][qq];
@@ -1171,6 +1172,383 @@ __global__ void __launch_bounds__(256) image_error_kernel(const float* __restric
     }
     __syncthreads();
   }
+}
+
+// ------------------------------------------------- pooled error term -------
+// ReprojectionErrorLoss with pooling=True (reference train/loss.py:405-434):
+// at every level the prediction, the image and the detached error map go
+// through AvgPool2d(3, stride 1) (valid: [h,w] -> [hp,wp] = [h-2,w-2]) and
+// the NLL, the edge-aware smoothness of sigma' and the F5 consistency of
+// sigma' against the opposite pooled disparity are evaluated on that grid.
+// Stages, each ONE launch over every level and the whole batch:
+//   pool_kernel        predictions, error map (and image when esw > 0) ->
+//                      caller workspace; zeroes the pooled-gradient cells
+//   pool_terms_kernel  the three terms as f64 block partials and, with GRAD,
+//                      the gradient w.r.t. sigma' per unit gout_err
+//   loss_scatter_kernel<false> on the pooled maps (GRAD, ecw > 0): the
+//                      consistency's sampled operand (d'_(1-v)) receives a
+//                      data-dependent scatter; on the pooled grid it is the
+//                      sigma term of the unpooled loss's scatter, so the
+//                      strip-owned kernel takes it as it is (LDS fixed-point
+//                      accumulators, every cell stored once, deterministic)
+//                      with the pooled predictions as its prediction, the
+//                      pooled-gradient cells as its output, no disparity
+//                      term (gout_disp null) and a device 1.0 as gout_err
+//   pool_adjoint_kernel  the pool adjoint as a gather (each pooled cell
+//                      spreads 1/9 onto its 3x3 inputs), added into dpred
+// (a first version scattered with int32 global atomics from
+// pool_terms_kernel: 282 us at B=8 256x512 against 24 us for pool_kernel)
+struct PArgs {
+  const float* pred[MAXS];  // NHWC [N][h][w][4]
+  const float* img[MAXS];   // [N][6][h][w]
+  const float* emap[MAXS];  // [N][2][h][w]
+  float* dpred[MAXS];       // adjoint target NHWC [N][h][w][4]
+  float4* pp[MAXS];         // pooled predictions [N][hp][wp]
+  float2* pe[MAXS];         // pooled error map [N][hp][wp]
+  float* pi[MAXS];          // pooled image [N][6][hp][wp] (esw > 0)
+  float4* pg[MAXS];  // d error_loss / d(pooled maps) per unit gout_err [N][hp][wp]
+  int h[MAXS], w[MAXS], block0[MAXS], cpi[MAXS];  // cpi: blocks per image
+  int nscales, N, nblocks;
+  int loss_type;
+  float esw, ecw, w_err;
+  double* parts;  // [nblocks][4] f64 partials: NLL, smoothness, consistency
+  float* out;     // [6]: out[1] and out[5] are (re)written
+  float* error_loss;
+  const float* gout_e;
+  float* one;  // a device 1.0f (the pooled scatter's gout_err), written by pool_kernel
+};
+
+constexpr int PNT = 256, PK = 4;  // threads per workgroup, cells per thread
+
+__device__ __forceinline__ int pscale_of(const PArgs& a, int b) {
+  int s = 0;
+#pragma unroll
+  for (int k = 1; k < MAXS; ++k)
+    if (k < a.nscales && b >= a.block0[k]) s = k;
+  return s;
+}
+
+// warp_tab with the sample column clamped to [-2, W+1] before the float ->
+// int conversion: any prediction value (a sigma of 1.5, an inf, a NaN) gives
+// in-range integers, and a clamped column has all four taps outside the
+// plane (they read as zero).  Inside [-1, W) it is warp_tab bit for bit.
+__device__ __forceinline__ Samp warp_clamped(float linx, const RowW& rw, float shift, int W) {
+  const float gx = 2.f * (linx + shift) - 1.f;
+  float ix = (gx + 1.f) * ((float)W * 0.5f) - 0.5f;
+  ix = fminf(fmaxf(ix, -2.f), (float)W + 1.f);
+  Samp t;
+  const float fx = floorf(ix);
+  t.x0 = (int)fx;
+  t.y0 = rw.y0;
+  t.w = ix - fx;
+  t.e = 1.f - t.w;
+  t.n = rw.n;
+  t.s = 1.f - rw.n;
+  return t;
+}
+
+__global__ void __launch_bounds__(PNT) pool_kernel(PArgs a) {
+  const int s = pscale_of(a, blockIdx.x);
+  const int h = pick(a.h, s), w = pick(a.w, s);
+  const int hp = h - 2, wp = w - 2, cells = hp * wp;
+  const int lb = blockIdx.x - pick(a.block0, s), cpi = pick(a.cpi, s);
+  const int n = lb / cpi, j0 = (lb - n * cpi) * (PNT * PK);
+  const float* pr = pick(a.pred, s) + (long)n * h * w * 4;
+  const float* em = pick(a.emap, s) + (long)n * 2 * h * w;
+  const float* im = pick(a.img, s) + (long)n * 6 * h * w;
+  float4* pp = pick(a.pp, s) + (long)n * cells;
+  float2* pe = pick(a.pe, s) + (long)n * cells;
+  float4* pg = pick(a.pg, s) + (long)n * cells;
+  float* pi = pick(a.pi, s);
+  constexpr float k9 = 1.f / 9.f;
+  if (blockIdx.x == 0 && threadIdx.x == 0) *a.one = 1.f;
+#pragma unroll 1
+  for (int k = 0; k < PK; ++k) {
+    const int j = j0 + k * PNT + (int)threadIdx.x;
+    if (j >= cells) break;
+    const int y = j / wp, x = j - y * wp;
+    float4 sp = make_float4(0.f, 0.f, 0.f, 0.f);
+    float e0 = 0.f, e1 = 0.f;
+#pragma unroll
+    for (int u = 0; u < 3; ++u)
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        const int o = (y + u) * w + x + q;
+        const float4 p = *reinterpret_cast<const float4*>(pr + o * 4);
+        sp.x += p.x; sp.y += p.y; sp.z += p.z; sp.w += p.w;
+        e0 += em[o];
+        e1 += em[h * w + o];
+      }
+    pp[j] = make_float4(sp.x * k9, sp.y * k9, sp.z * k9, sp.w * k9);
+    pe[j] = make_float2(e0 * k9, e1 * k9);
+    pg[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (pi != nullptr) {
+      float* po = pi + (long)n * 6 * cells + j;
+#pragma unroll 1
+      for (int c = 0; c < 6; ++c) {
+        const float* ip = im + c * h * w + y * w + x;
+        float sv = 0.f;
+#pragma unroll
+        for (int u = 0; u < 3; ++u)
+#pragma unroll
+          for (int q = 0; q < 3; ++q) sv += ip[u * w + q];
+        po[c * cells] = sv * k9;
+      }
+    }
+  }
+}
+
+template <bool GRAD>
+__global__ void __launch_bounds__(PNT) pool_terms_kernel(PArgs a) {
+  __shared__ double red[3][PNT / 64];
+  const int tid = threadIdx.x;
+  const int s = pscale_of(a, blockIdx.x);
+  const int H = pick(a.h, s) - 2, W = pick(a.w, s) - 2, HW = H * W;
+  const int lb = blockIdx.x - pick(a.block0, s), cpi = pick(a.cpi, s);
+  const int n = lb / cpi, j0 = (lb - n * cpi) * (PNT * PK);
+  const float4* P = pick(a.pp, s) + (long)n * HW;
+  const float2* E = pick(a.pe, s) + (long)n * HW;
+  float4* G = pick(a.pg, s) + (long)n * HW;
+  const float* pi = pick(a.pi, s);
+  const bool do_s = a.esw > 0.f && pi != nullptr, do_c = a.ecw > 0.f;
+  const double np = (double)a.N * HW;
+  const float kn = (float)(a.w_err / (2.0 * np));
+  const float kse = (float)(a.w_err * a.esw / np);
+  const float kce = (float)(a.w_err * a.ecw / np);
+  float acc[3] = {0.f, 0.f, 0.f};
+#pragma unroll 1
+  for (int k = 0; k < PK; ++k) {
+    const int j = j0 + k * PNT + tid;
+    if (j >= HW) break;
+    const int y = j / W, x = j - y * W;
+    const float4 p0 = P[j];
+    const float2 e0 = E[j];
+    const float4 pxp = P[min(j + 1, HW - 1)], pxm = P[max(j - 1, 0)];
+    const float4 pyp = P[min(j + W, HW - 1)], pym = P[max(j - W, 0)];
+    const float linx = lin01(x, W);
+    const RowW rw = row_w(y, H);
+    float gs[2] = {0.f, 0.f};
+#pragma unroll
+    for (int v = 0; v < 2; ++v) {
+      const float sg = comp(p0, 2 + v), ev = v == 0 ? e0.x : e0.y;
+      // ---- NLL on (sigma', pooled error) (loss.py:389-403)
+      {
+        float g;
+        if (a.loss_type == 1) {
+          acc[0] += fdiv(ev, sg) + __logf(sg);
+          g = fdiv(1.f, sg) - fdiv(ev, sg * sg);
+        } else if (a.loss_type == 2) {
+          const float ex = __expf(sg);
+          acc[0] += ev * ex + sg;
+          g = 0.5f * (ev * ex + 1.f);
+        } else {
+          acc[0] += fabsf(sg - ev);
+          g = sgnf(sg - ev);
+        }
+        if (GRAD) gs[v] += kn * g;
+      }
+      // ---- edge-aware smoothness of sigma' against the pooled image
+      if (do_s) {
+        const float* I = pi + ((long)n * 6 + v * 3) * HW + j;
+        float gx0 = 0.f, gx1 = 0.f, gy0 = 0.f, gy1 = 0.f;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const float* Ic = I + c * HW;
+          const float i0 = Ic[0];
+          gx0 += fabsf(i0 - Ic[x < W - 1 ? 1 : 0]);
+          gx1 += fabsf(Ic[x > 0 ? -1 : 0] - i0);
+          gy0 += fabsf(i0 - Ic[y < H - 1 ? W : 0]);
+          gy1 += fabsf(Ic[y > 0 ? -W : 0] - i0);
+        }
+        const float wx0 = x < W - 1 ? __expf(-gx0 * (1.f / 3.f)) : 0.f;
+        const float wx1 = x > 0 ? __expf(-gx1 * (1.f / 3.f)) : 0.f;
+        const float wy0 = y < H - 1 ? __expf(-gy0 * (1.f / 3.f)) : 0.f;
+        const float wy1 = y > 0 ? __expf(-gy1 * (1.f / 3.f)) : 0.f;
+        const float dxp = sg - comp(pxp, 2 + v), dxm = comp(pxm, 2 + v) - sg;
+        const float dyp = sg - comp(pyp, 2 + v), dym = comp(pym, 2 + v) - sg;
+        acc[1] += fabsf(dxp * wx0) + fabsf(dyp * wy0);  // the weights are 0 at the far edges
+        if (GRAD)
+          gs[v] += kse * (sgnf(dxp * wx0) * wx0 - sgnf(dxm * wx1) * wx1 + sgnf(dyp * wy0) * wy0 -
+                          sgnf(dym * wy1) * wy1);
+      }
+      // ---- consistency (F5): sigma'_v vs the opposite pooled disparity
+      // sampled at the shift sigma'_v; the taps are clamped, zero outside
+      if (do_c) {
+        const float sign = v == 0 ? -1.f : 1.f;
+        const Samp t = warp_clamped(linx, rw, sign * sg, W);
+        const float* opp = reinterpret_cast<const float*>(P) + (1 - v);
+        const float nw = ldc(opp, t.y0, t.x0, H, W, 4), ne = ldc(opp, t.y0, t.x0 + 1, H, W, 4);
+        const float sw = ldc(opp, t.y0 + 1, t.x0, H, W, 4);
+        const float se = ldc(opp, t.y0 + 1, t.x0 + 1, H, W, 4);
+        const float wv = nw * (t.s * t.e) + ne * (t.s * t.w) + sw * (t.n * t.e) + se * (t.n * t.w);
+        const float dix = t.s * (ne - nw) + t.n * (se - sw);
+        acc[2] += fabsf(sg - wv);
+        // (the sampled operand's gradient: the scatter launch that follows)
+        if (GRAD) gs[v] += sgnf(sg - wv) * kce * (1.f - dix * sign * (float)W);
+      }
+    }
+    if (GRAD) *reinterpret_cast<float2*>(reinterpret_cast<float*>(G + j) + 2) =
+        make_float2(gs[0], gs[1]);
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float tsum = wave_sum(acc[k]);
+    if ((tid & 63) == 0) red[k][tid >> 6] = (double)tsum;
+  }
+  __syncthreads();
+  if (tid < 3) {
+    double r = 0.0;
+    for (int wv = 0; wv < PNT / 64; ++wv) r += red[tid][wv];
+    a.parts[(long)blockIdx.x * 4 + tid] = r;
+  }
+}
+
+// out[1], out[5] and error_loss from the block partials: per level the means
+// (NLL over N*2*hp*wp, for log_bayesian / 2 again; smoothness and consistency
+// over N*hp*wp), every block in a fixed order
+__global__ void __launch_bounds__(PNT) pool_reduce_kernel(PArgs a) {
+  __shared__ double red[3][PNT / 64];
+  __shared__ double fac[MAXS][3];
+  const int tid = threadIdx.x;
+  if (tid < a.nscales * 3) {
+    const int s = tid / 3, k = tid - s * 3;
+    const double np = (double)a.N * (pick(a.h, s) - 2) * (pick(a.w, s) - 2);
+    fac[s][k] = (k == 0 ? (a.loss_type == 2 ? 0.25 : 0.5) : 1.0) / np;
+  }
+  __syncthreads();
+  double q[3] = {0, 0, 0};
+  for (int b = tid; b < a.nblocks; b += PNT) {
+    const int s = pscale_of(a, b);
+    const double2 v0 = *reinterpret_cast<const double2*>(a.parts + (long)b * 4);
+    const double v1 = a.parts[(long)b * 4 + 2];
+    q[0] += v0.x * fac[s][0];
+    q[1] += v0.y * fac[s][1];
+    q[2] += v1 * fac[s][2];
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) q[k] += __shfl_xor(q[k], o, 64);
+    if ((tid & 63) == 0) red[k][tid >> 6] = q[k];
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double f[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      f[k] = 0.0;
+      for (int wv = 0; wv < PNT / 64; ++wv) f[k] += red[k][wv];
+    }
+    double er = f[0];
+    if (a.esw > 0.f) er += (double)a.esw * f[1];
+    if (a.ecw > 0.f) er += (double)a.ecw * f[2];
+    a.out[1] = (float)(er * a.w_err);
+    a.out[5] = (float)er;
+    if (a.error_loss != nullptr) *a.error_loss = a.out[1];
+  }
+}
+
+// dpred += gout_err * (pool adjoint of pg): pixel (y, x) gathers the pooled
+// cells (y-2..y, x-2..x) that exist, 1/9 each
+__global__ void __launch_bounds__(PNT) pool_adjoint_kernel(PArgs a) {
+  const int s = pscale_of(a, blockIdx.x);
+  const int h = pick(a.h, s), w = pick(a.w, s);
+  const int hp = h - 2, wp = w - 2;
+  const int lb = blockIdx.x - pick(a.block0, s), cpi = pick(a.cpi, s);
+  const int n = lb / cpi, j0 = (lb - n * cpi) * (PNT * PK);
+  const float4* G = pick(a.pg, s) + (long)n * hp * wp;
+  float* dp = pick(a.dpred, s) + (long)n * h * w * 4;
+  const float kz = gval(a.gout_e) * (1.f / 9.f);
+#pragma unroll 1
+  for (int k = 0; k < PK; ++k) {
+    const int j = j0 + k * PNT + (int)threadIdx.x;
+    if (j >= h * w) break;
+    const int y = j / w, x = j - y * w;
+    float g0 = 0.f, g1 = 0.f, g2 = 0.f, g3 = 0.f;
+#pragma unroll
+    for (int u = 0; u < 3; ++u)
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        const int cy = y - u, cx = x - q;
+        const bool in = cy >= 0 && cy < hp && cx >= 0 && cx < wp;
+        const float4 c = G[min(max(cy, 0), hp - 1) * wp + min(max(cx, 0), wp - 1)];
+        g0 += in ? c.x : 0.f;
+        g1 += in ? c.y : 0.f;
+        g2 += in ? c.z : 0.f;
+        g3 += in ? c.w : 0.f;
+      }
+    float4 d = *reinterpret_cast<const float4*>(dp + j * 4);
+    d.x += kz * g0;
+    d.y += kz * g1;
+    d.z += kz * g2;
+    d.w += kz * g3;
+    *reinterpret_cast<float4*>(dp + j * 4) = d;
+  }
+}
+
+// workspace layout of the pooled stage (every section 16-byte aligned) and
+// the block mapping of its launches: a block covers PNT * PK cells of one
+// image of one level.  pooled: cells of the pooled grid, else of the level.
+struct PoolLayout {
+  size_t pp[MAXS], pe[MAXS], pi[MAXS], pg[MAXS], parts, one, total;
+};
+int pool_blocks(PArgs& a, int nscales, int N, int H0, int W0, bool pooled) {
+  a.nscales = nscales;
+  a.N = N;
+  int blocks = 0;
+  for (int s = 0; s < nscales; ++s) {
+    a.h[s] = H0 >> s;
+    a.w[s] = W0 >> s;
+    const long cells = pooled ? (long)(a.h[s] - 2) * (a.w[s] - 2) : (long)a.h[s] * a.w[s];
+    a.cpi[s] = ceil_div(cells, PNT * PK);
+    a.block0[s] = blocks;
+    blocks += N * a.cpi[s];
+  }
+  a.nblocks = blocks;
+  return blocks;
+}
+PoolLayout pool_layout(int nscales, int N, int H0, int W0) {
+  PoolLayout L{};
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    const size_t o = off;
+    off += (bytes + 15) & ~(size_t)15;
+    return o;
+  };
+  for (int s = 0; s < nscales; ++s) {
+    const size_t cells = (size_t)N * ((H0 >> s) - 2) * ((W0 >> s) - 2);
+    L.pp[s] = take(cells * sizeof(float4));
+    L.pe[s] = take(cells * sizeof(float2));
+    L.pi[s] = take(cells * 6 * sizeof(float));
+    L.pg[s] = take(cells * sizeof(float4));
+  }
+  PArgs a{};
+  L.parts = take((size_t)pool_blocks(a, nscales, N, H0, W0, true) * 4 * sizeof(double));
+  L.one = take(sizeof(float));
+  L.total = off;
+  return L;
+}
+void pool_args(PArgs& a, int nscales, int N, int H, int W, const float* const* img,
+               const float* const* pred, const float* const* emaps, float* const* dpred,
+               int loss_type, float esw, float ecw, float w_err, void* pool_ws) {
+  const PoolLayout L = pool_layout(nscales, N, H, W);
+  char* base = static_cast<char*>(pool_ws);
+  for (int s = 0; s < nscales; ++s) {
+    a.pred[s] = pred[s];
+    a.img[s] = img[s];
+    a.emap[s] = emaps ? emaps[s] : nullptr;
+    a.dpred[s] = dpred ? dpred[s] : nullptr;
+    a.pp[s] = reinterpret_cast<float4*>(base + L.pp[s]);
+    a.pe[s] = reinterpret_cast<float2*>(base + L.pe[s]);
+    a.pi[s] = esw > 0.f ? reinterpret_cast<float*>(base + L.pi[s]) : nullptr;
+    a.pg[s] = reinterpret_cast<float4*>(base + L.pg[s]);
+  }
+  a.parts = reinterpret_cast<double*>(base + L.parts);
+  a.one = reinterpret_cast<float*>(base + L.one);
+  a.loss_type = loss_type;
+  a.esw = esw;
+  a.ecw = ecw;
+  a.w_err = w_err;
 }
 
 inline int grid_for(long n) {
@@ -1278,21 +1656,20 @@ long um_loss_ws(int nscales, int N, int H, int W) {
          sizeof(double);
 }
 
-int um_loss_fwd(int nscales, int N, int H, int W, const float* const* img,
-                const float* const* pred, float alpha, int loss_type, float esw, float ecw,
-                float w_wssim, float w_cons, float w_smooth, float w_err, double* ws,
-                float* emap_last, float* const* recon_out, float* out, float* disp_loss,
-                float* error_loss, float* const* gpart, hipStream_t st) {
-  UM_CHECK_ARG(nscales >= 1 && nscales <= MAXS, "um_loss_fwd: %d scales (1..%d)", nscales, MAXS);
-  UM_CHECK_ARG((H >> (nscales - 1)) >= 3 && (W >> (nscales - 1)) >= 3,
-               "um_loss_fwd: image %dx%d too small for %d scales", H, W, nscales);
+// the launches of um_loss_fwd; emaps: per-scale error map outputs (null entries skipped)
+static int loss_fwd_launch(int nscales, int N, int H, int W, const float* const* img,
+                           const float* const* pred, float alpha, int loss_type, float esw,
+                           float ecw, float w_wssim, float w_cons, float w_smooth, float w_err,
+                           double* ws, float* const* emaps, float* const* recon_out, float* out,
+                           float* disp_loss, float* error_loss, float* const* gpart,
+                           hipStream_t st) {
   LArgs a{};
   const int blocks = gpart ? loss_setup(a, nscales, N, H, W, img, pred, nullptr, BTY, BTX)
                            : loss_setup(a, nscales, N, H, W, img, pred, nullptr, FTY, FTX);
   a.alpha = alpha; a.loss_type = loss_type; a.esw = esw; a.ecw = ecw;
   a.w_wssim = w_wssim; a.w_cons = w_cons; a.w_smooth = w_smooth; a.w_err = w_err;
   a.parts = ws;
-  a.emap = emap_last;
+  for (int l = 0; l < nscales; ++l) a.emap[l] = emaps[l];
   for (int l = 0; l < nscales; ++l) a.rec[l] = recon_out ? recon_out[l] : nullptr;
   a.out = out;
   a.disp_loss = disp_loss;
@@ -1308,21 +1685,22 @@ int um_loss_fwd(int nscales, int N, int H, int W, const float* const* img,
   return UM_OK;
 }
 
-int um_loss_bwd(int nscales, int N, int H, int W, const float* const* img,
+int um_loss_fwd(int nscales, int N, int H, int W, const float* const* img,
                 const float* const* pred, float alpha, int loss_type, float esw, float ecw,
-                float w_wssim, float w_cons, float w_smooth, float w_err,
-                const float* gout_disp, const float* gout_err, const float* const* gpart,
-                float* const* dpred, hipStream_t st) {
-  UM_CHECK_ARG(nscales >= 1 && nscales <= MAXS, "um_loss_bwd: %d scales (1..%d)", nscales, MAXS);
+                float w_wssim, float w_cons, float w_smooth, float w_err, double* ws,
+                float* emap_last, float* const* recon_out, float* out, float* disp_loss,
+                float* error_loss, float* const* gpart, hipStream_t st) {
+  UM_CHECK_ARG(nscales >= 1 && nscales <= MAXS, "um_loss_fwd: %d scales (1..%d)", nscales, MAXS);
   UM_CHECK_ARG((H >> (nscales - 1)) >= 3 && (W >> (nscales - 1)) >= 3,
-               "um_loss_bwd: image %dx%d too small for %d scales", H, W, nscales);
-  const size_t lds = (size_t)(STR + 2) * W * 2 * sizeof(int);
-  UM_CHECK_ARG(lds <= 128 * 1024, "um_loss_bwd: width %d too large", W);
-  LArgs a{};
-  a.alpha = alpha; a.loss_type = loss_type; a.esw = esw; a.ecw = ecw;
-  a.w_wssim = w_wssim; a.w_cons = w_cons; a.w_smooth = w_smooth; a.w_err = w_err;
-  a.gout_d = gout_disp;
-  a.gout_e = gout_err;
+               "um_loss_fwd: image %dx%d too small for %d scales", H, W, nscales);
+  float* emaps[MAXS] = {};
+  emaps[nscales - 1] = emap_last;
+  return loss_fwd_launch(nscales, N, H, W, img, pred, alpha, loss_type, esw, ecw, w_wssim, w_cons,
+                         w_smooth, w_err, ws, emaps, recon_out, out, disp_loss, error_loss, gpart,
+                         st);
+}
+
+static void scatter_lds_attr() {
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&loss_scatter_kernel<false>),
@@ -1331,6 +1709,21 @@ int um_loss_bwd(int nscales, int N, int H, int W, const float* const* img,
                               hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
     attr = true;
   }
+}
+
+// the launches of um_loss_bwd
+static int loss_bwd_launch(int nscales, int N, int H, int W, const float* const* img,
+                           const float* const* pred, float alpha, int loss_type, float esw,
+                           float ecw, float w_wssim, float w_cons, float w_smooth, float w_err,
+                           const float* gout_disp, const float* gout_err,
+                           const float* const* gpart, float* const* dpred, hipStream_t st) {
+  const size_t lds = (size_t)(STR + 2) * W * 2 * sizeof(int);
+  LArgs a{};
+  a.alpha = alpha; a.loss_type = loss_type; a.esw = esw; a.ecw = ecw;
+  a.w_wssim = w_wssim; a.w_cons = w_cons; a.w_smooth = w_smooth; a.w_err = w_err;
+  a.gout_d = gout_disp;
+  a.gout_e = gout_err;
+  scatter_lds_attr();
   int blocks = loss_setup(a, nscales, N, H, W, img, pred, dpred, STR, 0);
   if (gpart) {
     // the fused forward computed every other term: the scatter completes them
@@ -1342,6 +1735,133 @@ int um_loss_bwd(int nscales, int N, int H, int W, const float* const* img,
     blocks = loss_setup(a, nscales, N, H, W, img, pred, dpred, BTY, BTX);
     hipLaunchKernelGGL(loss_grad_kernel<false>, dim3(blocks), dim3(BNT), 0, st, a);
   }
+  UM_LAUNCH_CHECK();
+  return UM_OK;
+}
+
+int um_loss_bwd(int nscales, int N, int H, int W, const float* const* img,
+                const float* const* pred, float alpha, int loss_type, float esw, float ecw,
+                float w_wssim, float w_cons, float w_smooth, float w_err,
+                const float* gout_disp, const float* gout_err, const float* const* gpart,
+                float* const* dpred, hipStream_t st) {
+  UM_CHECK_ARG(nscales >= 1 && nscales <= MAXS, "um_loss_bwd: %d scales (1..%d)", nscales, MAXS);
+  UM_CHECK_ARG((H >> (nscales - 1)) >= 3 && (W >> (nscales - 1)) >= 3,
+               "um_loss_bwd: image %dx%d too small for %d scales", H, W, nscales);
+  UM_CHECK_ARG((size_t)(STR + 2) * W * 2 * sizeof(int) <= 128 * 1024,
+               "um_loss_bwd: width %d too large", W);
+  return loss_bwd_launch(nscales, N, H, W, img, pred, alpha, loss_type, esw, ecw, w_wssim, w_cons,
+                         w_smooth, w_err, gout_disp, gout_err, gpart, dpred, st);
+}
+
+// ---- pooling=True (loss.py:405-434): the disparity loss from the launches
+// above with the error term switched off (weight 0, l1 form: every factor
+// finite), the error term from the pooled stage
+static bool pool_geom_ok(int nscales, int H, int W) {
+  return nscales >= 1 && nscales <= MAXS && (H >> (nscales - 1)) >= 4 &&
+         (W >> (nscales - 1)) >= 4;
+}
+
+// the gradient w.r.t. the sampled pooled disparity, per unit gout_err, into
+// channels 0/1 of the pooled-gradient cells: loss_scatter_kernel<false> with
+// the pooled maps as its level geometry (strips of STR rows, full width)
+static void pool_scatter_launch(const PArgs& p, hipStream_t st) {
+  scatter_lds_attr();
+  LArgs a{};
+  a.nscales = p.nscales;
+  a.N = p.N;
+  int blocks = 0;
+  for (int s = 0; s < p.nscales; ++s) {
+    a.pred[s] = reinterpret_cast<const float*>(p.pp[s]);
+    a.dpred[s] = reinterpret_cast<float*>(p.pg[s]);
+    a.h[s] = p.h[s] - 2;
+    a.w[s] = p.w[s] - 2;
+    a.tiles_x[s] = 1;
+    a.tiles_y[s] = ceil_div(a.h[s], STR);
+    a.block0[s] = blocks;
+    blocks += p.N * a.tiles_y[s];
+  }
+  a.nblocks = blocks;
+  a.ecw = p.ecw;
+  a.w_err = p.w_err;
+  a.gout_e = p.one;  // gout_d null: no disparity term
+  const size_t lds = (size_t)(STR + 2) * a.w[0] * 2 * sizeof(int);
+  hipLaunchKernelGGL(loss_scatter_kernel<false>, dim3(blocks), dim3(SCT), lds, st, a);
+}
+
+long um_loss_pool_ws(int nscales, int N, int H, int W) {
+  if (!pool_geom_ok(nscales, H, W) || N < 1) return 0;
+  return (long)pool_layout(nscales, N, H, W).total;
+}
+
+int um_loss_pool_fwd(int nscales, int N, int H, int W, const float* const* img,
+                     const float* const* pred, float alpha, int loss_type, float esw, float ecw,
+                     float w_wssim, float w_cons, float w_smooth, float w_err, double* ws,
+                     float* const* emaps, float* const* recon_out, float* out, float* disp_loss,
+                     float* error_loss, float* const* gpart, void* pool_ws, hipStream_t st) {
+  UM_CHECK_ARG(pool_geom_ok(nscales, H, W),
+               "um_loss_pool_fwd: %d scales of %dx%d (1..%d scales, the last at least 4x4)",
+               nscales, H, W, MAXS);
+  UM_CHECK_ARG((size_t)(STR + 2) * W * 2 * sizeof(int) <= 128 * 1024,
+               "um_loss_pool_fwd: width %d too large", W);
+  UM_CHECK_ARG(pool_ws != nullptr && (reinterpret_cast<uintptr_t>(pool_ws) & 15) == 0,
+               "um_loss_pool_fwd: pool_ws must be 16-byte aligned");
+  for (int l = 0; l < nscales; ++l)
+    UM_CHECK_ARG(emaps != nullptr && emaps[l] != nullptr,
+                 "um_loss_pool_fwd: the error map of every scale is needed (scale %d)", l);
+  const int rc = loss_fwd_launch(nscales, N, H, W, img, pred, alpha, 0, 0.f, 0.f, w_wssim, w_cons,
+                                 w_smooth, 0.f, ws, emaps, recon_out, out, disp_loss, nullptr,
+                                 gpart, st);
+  if (rc != UM_OK) return rc;
+  PArgs p{};
+  pool_args(p, nscales, N, H, W, img, pred, emaps, nullptr, loss_type, esw, ecw, w_err, pool_ws);
+  p.out = out;
+  p.error_loss = error_loss;
+  const int blocks = pool_blocks(p, nscales, N, H, W, true);
+  hipLaunchKernelGGL(pool_kernel, dim3(blocks), dim3(PNT), 0, st, p);
+  if (gpart) {
+    hipLaunchKernelGGL(pool_terms_kernel<true>, dim3(blocks), dim3(PNT), 0, st, p);
+    if (ecw > 0.f) pool_scatter_launch(p, st);
+  } else {
+    hipLaunchKernelGGL(pool_terms_kernel<false>, dim3(blocks), dim3(PNT), 0, st, p);
+  }
+  hipLaunchKernelGGL(pool_reduce_kernel, dim3(1), dim3(PNT), 0, st, p);
+  UM_LAUNCH_CHECK();
+  return UM_OK;
+}
+
+int um_loss_pool_bwd(int nscales, int N, int H, int W, const float* const* img,
+                     const float* const* pred, float alpha, int loss_type, float esw, float ecw,
+                     float w_wssim, float w_cons, float w_smooth, float w_err,
+                     const float* gout_disp, const float* gout_err, const float* const* gpart,
+                     const float* const* emaps, void* pool_ws, float* const* dpred,
+                     hipStream_t st) {
+  UM_CHECK_ARG(pool_geom_ok(nscales, H, W),
+               "um_loss_pool_bwd: %d scales of %dx%d (1..%d scales, the last at least 4x4)",
+               nscales, H, W, MAXS);
+  UM_CHECK_ARG((size_t)(STR + 2) * W * 2 * sizeof(int) <= 128 * 1024,
+               "um_loss_pool_bwd: width %d too large", W);
+  UM_CHECK_ARG(pool_ws != nullptr && (reinterpret_cast<uintptr_t>(pool_ws) & 15) == 0,
+               "um_loss_pool_bwd: pool_ws must be 16-byte aligned");
+  if (!gpart && gout_err)
+    for (int l = 0; l < nscales; ++l)
+      UM_CHECK_ARG(emaps != nullptr && emaps[l] != nullptr,
+                   "um_loss_pool_bwd: without gpart the error map of every scale is needed "
+                   "(scale %d)", l);
+  const int rc = loss_bwd_launch(nscales, N, H, W, img, pred, alpha, 0, 0.f, 0.f, w_wssim, w_cons,
+                                 w_smooth, 0.f, gout_disp, gout_err, gpart, dpred, st);
+  if (rc != UM_OK) return rc;
+  if (!gout_err) return UM_OK;  // nothing flows into the error term
+  PArgs p{};
+  pool_args(p, nscales, N, H, W, img, pred, emaps, dpred, loss_type, esw, ecw, w_err, pool_ws);
+  p.gout_e = gout_err;
+  if (!gpart) {  // the forward left no pooled gradient: pool and differentiate now
+    const int blocks = pool_blocks(p, nscales, N, H, W, true);
+    hipLaunchKernelGGL(pool_kernel, dim3(blocks), dim3(PNT), 0, st, p);
+    hipLaunchKernelGGL(pool_terms_kernel<true>, dim3(blocks), dim3(PNT), 0, st, p);
+    if (ecw > 0.f) pool_scatter_launch(p, st);
+  }
+  const int blocks = pool_blocks(p, nscales, N, H, W, false);
+  hipLaunchKernelGGL(pool_adjoint_kernel, dim3(blocks), dim3(PNT), 0, st, p);
   UM_LAUNCH_CHECK();
   return UM_OK;
 }

@@ -120,15 +120,15 @@ class ReprojectionErrorLoss(_FusedOnly):
         super().__init__()
         if loss_type not in ('l1', 'bayesian', 'log_bayesian'):
             raise ValueError('Loss must be either "l1", "bayesian" or "log_bayesian".')
-        if pooling:
-            raise NotImplementedError('umamd ReprojectionErrorLoss: pooling=True is not '
-                                      'implemented (every reference config uses False)')
         self.loss_type = loss_type
         self.smoothness_weight = smoothness_weight
         self.consistency_weight = consistency_weight
         self.smoothness = SmoothnessLoss() if smoothness_weight > 0 else None
         self.consistency = ConsistencyLoss() if consistency_weight > 0 else None
-        self.pool = nn.Identity()
+        # pooling (reference :405-434): every level's prediction, image and
+        # error map are 3x3 average-pooled before the error term; evaluated
+        # by the pooled stage of the fused loss (um_loss_pool_fwd / _bwd)
+        self.pool = nn.AvgPool2d(kernel_size=3, stride=1) if pooling else nn.Identity()
 
 
 class TukraUncertaintyLoss(nn.Module):
@@ -162,7 +162,8 @@ class TukraUncertaintyLoss(nn.Module):
                 'esw': float(pe.smoothness_weight), 'ecw': float(pe.consistency_weight),
                 'w_wssim': float(self.wssim_weight), 'w_cons': float(self.consistency_weight),
                 'w_smooth': float(self.smoothness_weight),
-                'w_err': float(self.predictive_error_weight)}
+                'w_err': float(self.predictive_error_weight),
+                'pool': isinstance(pe.pool, nn.AvgPool2d)}
 
     def forward(self, image_pyramid: ImagePyramid, predictions: ImagePyramid,
                 recon_pyramid: ImagePyramid, epoch: Optional[int] = None,

@@ -9,6 +9,9 @@
                             and ONE backward launch producing the gradient
                             w.r.t. all four prediction channels of every scale,
                             including the WSSIM term's path through the warp.
+                            ``cfg['pool']`` (ReprojectionErrorLoss(pooling=True),
+                            loss.py:405-434): the error term on 3x3 average
+                            pools, um_loss_pool_fwd / um_loss_pool_bwd
   * ``image_error``         WeightedSSIMLoss.image_error (loss.py:96-131) of an
                             explicit recon (evaluation)
 
@@ -234,7 +237,18 @@ class TukraLossFn(torch.autograd.Function):
         dev = preds[0].device
         ws = torch.empty((max(query('um_loss_ws', n, N, H, W), 8) // 8,), dtype=torch.float64,
                          device=dev)
-        emap = torch.empty((N, 2, H >> (n - 1), W >> (n - 1)), dtype=torch.float32, device=dev)
+        pool = bool(cfg.get('pool'))
+        emaps = None
+        if pool:
+            # the pooled error term needs the error map of every level
+            emaps = [torch.empty((N, 2, H >> i, W >> i), dtype=torch.float32, device=dev)
+                     for i in range(n)]
+            emap = emaps[-1]
+            pws = torch.empty((query('um_loss_pool_ws', n, N, H, W),), dtype=torch.uint8,
+                              device=dev)
+        else:
+            emap = torch.empty((N, 2, H >> (n - 1), W >> (n - 1)), dtype=torch.float32, device=dev)
+            pws = None
         out = torch.empty(6, dtype=torch.float32, device=dev)
         dl = torch.empty((), dtype=torch.float32, device=dev)
         el = torch.empty_like(dl)
@@ -245,14 +259,23 @@ class TukraLossFn(torch.autograd.Function):
         if grad:
             gpart = [torch.empty((N, H >> i, W >> i, 4), dtype=torch.float32, device=dev)
                      for i in range(n)]
-        call('um_loss_fwd', n, N, H, W, _parr(pyr), _parr(preds), cfg['alpha'],
-             cfg['loss_type'], cfg['esw'], cfg['ecw'], cfg['w_wssim'], cfg['w_cons'],
-             cfg['w_smooth'], cfg['w_err'], ptr(ws), ptr(emap), rarr, ptr(out), ptr(dl),
-             ptr(el), _parr(gpart) if gpart is not None else None)
+        if pool:
+            call('um_loss_pool_fwd', n, N, H, W, _parr(pyr), _parr(preds), cfg['alpha'],
+                 cfg['loss_type'], cfg['esw'], cfg['ecw'], cfg['w_wssim'], cfg['w_cons'],
+                 cfg['w_smooth'], cfg['w_err'], ptr(ws), _parr(emaps), rarr, ptr(out), ptr(dl),
+                 ptr(el), _parr(gpart) if gpart is not None else None, ptr(pws))
+        else:
+            call('um_loss_fwd', n, N, H, W, _parr(pyr), _parr(preds), cfg['alpha'],
+                 cfg['loss_type'], cfg['esw'], cfg['ecw'], cfg['w_wssim'], cfg['w_cons'],
+                 cfg['w_smooth'], cfg['w_err'], ptr(ws), ptr(emap), rarr, ptr(out), ptr(dl),
+                 ptr(el), _parr(gpart) if gpart is not None else None)
         ctx.cfg = cfg
         ctx.n = n
         ctx.geom = (N, H, W)
         ctx.gpart = gpart
+        # pooled: the forward's gradient w.r.t. the pooled maps (in pws) and the
+        # error maps (a backward without partials pools them again)
+        ctx.pool = (emaps, pws) if pool else None
         ctx.save_for_backward(*preds, *pyr)
         ctx.mark_non_differentiable(out, emap)
         return dl, el, out, emap
@@ -270,11 +293,20 @@ class TukraLossFn(torch.autograd.Function):
         grads = [torch.empty((N, H >> i, W >> i, 4), dtype=torch.float32, device=dev)
                  for i in range(n)]
         gpart, ctx.gpart = ctx.gpart, None
-        call('um_loss_bwd', n, N, H, W, _parr(pyr), _parr(preds), cfg['alpha'],
-             cfg['loss_type'], cfg['esw'], cfg['ecw'], cfg['w_wssim'], cfg['w_cons'],
-             cfg['w_smooth'], cfg['w_err'], ptr(gd) if gd is not None else None,
-             ptr(ge) if ge is not None else None,
-             _parr(gpart) if gpart is not None else None, _parr(grads))
+        if ctx.pool is not None:
+            emaps, pws = ctx.pool
+            call('um_loss_pool_bwd', n, N, H, W, _parr(pyr), _parr(preds), cfg['alpha'],
+                 cfg['loss_type'], cfg['esw'], cfg['ecw'], cfg['w_wssim'], cfg['w_cons'],
+                 cfg['w_smooth'], cfg['w_err'], ptr(gd) if gd is not None else None,
+                 ptr(ge) if ge is not None else None,
+                 _parr(gpart) if gpart is not None else None, _parr(emaps), ptr(pws),
+                 _parr(grads))
+        else:
+            call('um_loss_bwd', n, N, H, W, _parr(pyr), _parr(preds), cfg['alpha'],
+                 cfg['loss_type'], cfg['esw'], cfg['ecw'], cfg['w_wssim'], cfg['w_cons'],
+                 cfg['w_smooth'], cfg['w_err'], ptr(gd) if gd is not None else None,
+                 ptr(ge) if ge is not None else None,
+                 _parr(gpart) if gpart is not None else None, _parr(grads))
         return (None, None, None, None, *[g.permute(0, 3, 1, 2) for g in grads],
                 *([None] * n))
 
@@ -286,6 +318,14 @@ def tukra_loss(cfg: dict, preds, pyramid, recon_out=None):
     n = len(preds)
     if not 1 <= n <= MAX_LEVELS:
         raise L.UmamdError(f'tukra_loss: {n} scales (1..{MAX_LEVELS})')
+    if cfg.get('pool'):
+        # AvgPool2d(3, stride 1) leaves [h-2, w-2]; the warp and the replicate-
+        # padded gradients on that grid need at least 2x2
+        for i, p in enumerate(preds):
+            h, w = p.shape[-2:]
+            if h < 4 or w < 4:
+                raise ValueError(f'tukra_loss: pooling=True needs every level to be at least '
+                                 f'4x4; level {i} is {h}x{w}')
     # the gradient partials are computed with the forward when it will be differentiated
     grad = torch.is_grad_enabled() and any(p.requires_grad for p in preds)
     out = TukraLossFn.apply(cfg, n, recon_out, grad, *preds, *[p.detach() for p in pyramid])
