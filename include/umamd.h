@@ -531,6 +531,88 @@ int um_loss_pool_bwd(int nscales, int N, int H, int W, const float* const* img,
 int um_image_error(const float* img, const float* rec, int N, int H, int W, float alpha,
                    float* out, hipStream_t stream);
 
+/* -------------------------------------------------------- loss terms ---
+ * The sub-losses of train/loss.py as standalone, differentiable entries
+ * (csrc/lossterms.hip): what a composition other than the fused
+ * TukraUncertaintyLoss above is built from.  Strided [N][C][h][w] operands
+ * are given as pointer + image stride (sn) + channel stride (sc) + pixel
+ * stride (sp): element (n, c, y, x) at p[n*sn + c*sc + (y*w + x)*sp], so
+ * channel slices of an NHWC prediction are passed without a copy.  A scalar
+ * is accumulated as one f64 partial per workgroup in ws (um_lossterm_ws(N, H,
+ * W) bytes, any term of that geometry) and finished on the device into a f32
+ * device scalar; an upstream scalar gradient g is a device pointer.  No entry
+ * allocates or synchronises.  Launches: forward = term + finish, backward =
+ * one adjoint launch (+ the scatter where an image is sampled).
+ */
+long um_lossterm_ws(int N, int H, int W);
+/* WeightedSSIMLoss.image_error (loss.py:96-131, ssim/dssim :43-90) with
+ * c1 = k1^2, c2 = k2^2 at run time: out [N][2][H][W], one launch; with ws and
+ * mean_out (both or neither) the same launch leaves the block partials of
+ * mean(e_L + e_R) (WeightedSSIMLoss.forward, loss.py:133-151) and a finish
+ * launch writes mean_out.  H, W >= 3 */
+int um_image_error_k(const float* img, const float* rec, int N, int H, int W, float alpha,
+                     float c1, float c2, float* out, double* ws, float* mean_out,
+                     hipStream_t stream);
+/* its adjoint w.r.t. rec (wrt 0) or img (wrt 1), grad [N][6][H][W], one launch.
+ * Upstream gradient of the map: g [N][2][H][W] (or NULL) plus g_mean[0] / (N*H*W)
+ * (or NULL: the mean's path).  L1 part: (1-alpha)/3 sign(X-Y) g, sign(0) = 0;
+ * SSIM part: alpha/3 times the sum over the <= 9 SSIM-grid cells whose window
+ * covers the pixel of G(cell) d(dssim_c(cell))/dX(pixel), G the adjoint of the
+ * align_corners resize (H-2)x(W-2) -> HxW applied to the upstream gradient;
+ * the clamp passes gradient where 0 <= (1-ssim)/2 <= 1 */
+int um_image_error_bwd(const float* img, const float* rec, int N, int H, int W, float alpha,
+                       float c1, float c2, int wrt, const float* g, const float* g_mean,
+                       float* grad, hipStream_t stream);
+/* adjoint of um_warp w.r.t. the sampled image (F.grid_sample's image gradient,
+ * utils.py:65-97): gimg[n][c] = sum over source pixels of gout[n][c][y][x] *
+ * w_tap at the four bilinear taps; taps outside the image receive nothing.
+ * One workgroup owns one target row of one image: the source rows t-1, t, t+1
+ * (the only ones whose row taps reach t; the row taps do not depend on the
+ * shift) scatter along x into f32 row accumulators in LDS, in that order, and
+ * every output element is stored exactly once: nothing is pre-zeroed and no
+ * global atomic is used.  The last bits depend on the arrival order of the LDS
+ * adds within a row (as grid_sample's own backward).  The C*W accumulators
+ * must fit 64 KiB of LDS: C*W <= um_warp_bwd_img_max_cw() = 16384 (W <= 5461
+ * at C = 3); a larger C*W is UM_ERR_ARG naming the limit, and nothing is
+ * launched */
+int um_warp_bwd_img_max_cw(void);
+int um_warp_bwd_img(const float* gout, int N, int C, int H, int W, const float* disp,
+                    long disp_sn, long disp_sp, float sign, float* gimg, hipStream_t stream);
+/* ConsistencyLoss.forward(disp, images) (loss.py:167-188): out[0] =
+ * mean|d_L - warp(i_R, -d_L)| + mean|d_R - warp(i_L, +d_R)|; disp and images
+ * strided [N][2][H][W] and may alias (images=None: the F5 quirk, disp is both
+ * the compared map and the sampled one).  H, W >= 2 */
+int um_consistency_fwd(const float* disp, long d_sn, long d_sc, long d_sp, const float* images,
+                       long i_sn, long i_sc, long i_sp, int N, int H, int W, double* ws,
+                       float* out, hipStream_t stream);
+/* gdisp [N][2][H][W] (or NULL) = the direct sign term + the shift term
+ * (d(warp)/d(shift) * sign * W); gimages [N][2][H][W] (or NULL) = the scatter
+ * of -sign(r) g/(NHW) through the taps (the um_warp_bwd_img rows, W <= 16384),
+ * staged in scratch [N][2][H][W].  alias != 0 (images is disp): gimages
+ * receives the sum of both, gdisp the direct part only */
+int um_consistency_bwd(const float* disp, long d_sn, long d_sc, long d_sp, const float* images,
+                       long i_sn, long i_sc, long i_sp, int N, int H, int W, const float* g,
+                       float* gdisp, float* gimages, float* scratch, int alias,
+                       hipStream_t stream);
+/* SmoothnessLoss.forward(disp, images) (loss.py:208-264): replicate-padded
+ * forward differences of disp (strided [N][2][H][W]) weighted by
+ * exp(-mean_c |grad I|), images [N][6][H][W]; out[0] = mean(e_L + e_R).  The
+ * gradient is w.r.t. disp only ([N][2][H][W]).  H, W >= 2 */
+int um_smoothness_fwd(const float* disp, long d_sn, long d_sc, long d_sp, const float* images,
+                      int N, int H, int W, double* ws, float* out, hipStream_t stream);
+int um_smoothness_bwd(const float* disp, long d_sn, long d_sc, long d_sp, const float* images,
+                      int N, int H, int W, const float* g, float* gdisp, hipStream_t stream);
+/* ReprojectionErrorLoss.l1 / .bayesian / .log_bayesian (loss.py:389-403) of
+ * (uncertainty, error), both strided [N][2][H][W]; loss_type as above.  The
+ * gradient is w.r.t. the uncertainty ([N][2][H][W]); the error is detached by
+ * definition (loss.py:418) */
+int um_nll_fwd(const float* unc, long u_sn, long u_sc, long u_sp, const float* err, long e_sn,
+               long e_sc, long e_sp, int N, int H, int W, int loss_type, double* ws, float* out,
+               hipStream_t stream);
+int um_nll_bwd(const float* unc, long u_sn, long u_sc, long u_sp, const float* err, long e_sn,
+               long e_sc, long e_sp, int N, int H, int W, int loss_type, const float* g,
+               float* gunc, hipStream_t stream);
+
 /* ------------------------------------------------------- adversarial ---
  * RandomDiscriminator pieces around its EncoderStages (reference
  * model/discriminator.py:53-86, train/loss.py:267-337).

@@ -7,10 +7,16 @@ all four channels of every scale, including the WSSIM term's path through
 the warp, both L-R consistency terms (with the scatter into the warped
 disparity), the edge-aware smoothness and the reprojection-error NLL.
 
-The sub-loss modules keep the reference's names and constructor kwargs so
-configs and attribute access (``loss.wssim.previous_image_error``,
-``loss.predictive_error.loss_type``...) work; the sub-losses are evaluated
-inside the fused kernels, not through their own ``forward``.
+That fused path is taken when ``recon_pyramid`` is the (tagged) output of
+``reconstruct_pyramid(predictions, image_pyramid)``, which is what the
+reference's own training loop passes.
+
+The sub-loss modules keep the reference's names, constructor kwargs and
+attributes (``loss.wssim.previous_image_error``,
+``loss.predictive_error.loss_type``...) and each has a standalone,
+differentiable ``forward`` on its own HIP kernels (umamd.lossterms), so they
+compose as the reference's do; ``TukraUncertaintyLoss.forward`` with any other
+recon runs the reference's per-level loop over them.
 """
 from typing import Optional
 
@@ -22,25 +28,19 @@ from torch.nn.parallel import DistributedDataParallel
 
 from umamd import discfn as DF
 from umamd import lossfn as LF
+from umamd import lossterms as LT
 from umamd import packer as P
 
 from .utils import ImagePyramid
 
 
-class _FusedOnly(nn.Module):
-    def forward(self, *args, **kwargs):
-        raise NotImplementedError(
-            f'umamd: {type(self).__name__} is evaluated inside TukraUncertaintyLoss\'s fused '
-            f'HIP kernels; a standalone forward is not implemented')
-
-
-class WeightedSSIMLoss(_FusedOnly):
-    """SSIM/L1 photometric error (reference :15-151)."""
+class WeightedSSIMLoss(nn.Module):
+    """SSIM/L1 photometric error (reference :15-151).  ``image_error`` and
+    ``forward`` are HIP kernels (um_image_error_k / _bwd) with ``alpha``,
+    ``k1``, ``k2`` at run time, differentiable w.r.t. both arguments."""
 
     def __init__(self, alpha: float = 0.85, k1: float = 0.01, k2: float = 0.03) -> None:
         super().__init__()
-        if k1 != 0.01 or k2 != 0.03:
-            raise NotImplementedError('umamd WeightedSSIMLoss: k1/k2 are compiled in (0.01, 0.03)')
         self.alpha = alpha
         self.k1 = k1 ** 2
         self.k2 = k2 ** 2
@@ -52,21 +52,55 @@ class WeightedSSIMLoss(_FusedOnly):
         """Error map [B,2,h,w] of the last scale evaluated (reference :38-41)."""
         return self._previous_image_error
 
+    # ssim, dssim, l1_error: torch ops on the device (on no hot path)
+    def ssim(self, x: Tensor, y: Tensor) -> Tensor:
+        """Per-pixel SSIM on the 3x3-pooled grid [N,C,H-2,W-2] (reference :43-74)."""
+        mx, my = self.pool(x), self.pool(y)
+        vx = self.pool(x * x) - mx * mx
+        vy = self.pool(y * y) - my * my
+        vxy = self.pool(x * y) - mx * my
+        return ((2 * mx * my + self.k1) * (2 * vxy + self.k2)) / \
+            ((mx * mx + my * my + self.k1) * (vx + vy + self.k2))
+
+    def dssim(self, x: Tensor, y: Tensor) -> Tensor:
+        """clamp((1 - SSIM) / 2, 0, 1) (reference :76-90)."""
+        return torch.clamp((1 - self.ssim(x, y)) / 2, 0, 1)
+
+    def l1_error(self, x: Tensor, y: Tensor) -> Tensor:
+        return (x - y).abs()
+
     def image_error(self, images: Tensor, recon: Tensor) -> Tensor:
         """Per-pixel alpha*DSSIM(upsampled) + (1-alpha)*L1, channel mean per
-        view -> [B,2,H,W] (reference :96-131); no gradient (evaluation)."""
-        if torch.is_grad_enabled() and (images.requires_grad or recon.requires_grad):
-            raise NotImplementedError('umamd WeightedSSIMLoss.image_error has no autograd '
-                                      '(training evaluates it inside TukraUncertaintyLoss)')
-        return LF.image_error(images, recon, self.alpha)
+        view -> [B,2,H,W] (reference :96-131).  Without a gradient to record
+        and with the default constants this stays the evaluation entry
+        (um_image_error), whose bits the evaluation engine reproduces."""
+        LT.check_hw('WeightedSSIMLoss.image_error', images, 3)
+        grad = torch.is_grad_enabled() and (images.requires_grad or recon.requires_grad)
+        if not grad and (self.k1, self.k2) == (0.01 ** 2, 0.03 ** 2):
+            return LF.image_error(images, recon, self.alpha)
+        return LT.image_error(images, recon, self.alpha, self.k1, self.k2)
+
+    def forward(self, images: Tensor, recon: Tensor) -> Tensor:
+        """mean(e_L + e_R) (reference :133-151); ``previous_image_error`` keeps
+        the map with its autograd history."""
+        loss, error = LT.wssim(images, recon, self.alpha, self.k1, self.k2)
+        self._previous_image_error = error
+        return loss
 
 
-class ConsistencyLoss(_FusedOnly):
-    """L-R consistency (reference :154-188)."""
+class ConsistencyLoss(nn.Module):
+    """L-R consistency (reference :154-188): um_consistency_fwd / _bwd."""
+
+    def forward(self, disp: Tensor, images: Optional[Tensor] = None) -> Tensor:
+        return LT.consistency(disp, images)
 
 
-class SmoothnessLoss(_FusedOnly):
-    """Edge-aware smoothness (reference :191-264)."""
+class SmoothnessLoss(nn.Module):
+    """Edge-aware smoothness (reference :191-264): um_smoothness_fwd / _bwd.
+    Differentiable w.r.t. ``disp``; ``images`` is data."""
+
+    def forward(self, disp: Tensor, images: Tensor) -> Tensor:
+        return LT.smoothness(disp, images)
 
 
 def _disc_module(disc: Module) -> Module:
@@ -112,8 +146,11 @@ class GeneratorLoss(nn.Module):
         return self.adversarial(predictions, labels)
 
 
-class ReprojectionErrorLoss(_FusedOnly):
-    """Uncertainty loss (reference :340-434)."""
+class ReprojectionErrorLoss(nn.Module):
+    """Uncertainty loss (reference :340-434).  ``forward``: the NLL
+    (um_nll_fwd / _bwd), the smoothness and the consistency of the uncertainty
+    on the HIP terms; ``self.pool``, the channel split and the scalar
+    arithmetic are ATen."""
 
     def __init__(self, loss_type: str = 'l1', smoothness_weight: float = 1.0,
                  consistency_weight: float = 1.0, pooling: bool = False) -> None:
@@ -129,6 +166,28 @@ class ReprojectionErrorLoss(_FusedOnly):
         # error map are 3x3 average-pooled before the error term; evaluated
         # by the pooled stage of the fused loss (um_loss_pool_fwd / _bwd)
         self.pool = nn.AvgPool2d(kernel_size=3, stride=1) if pooling else nn.Identity()
+
+    def loss_function(self, predicted: Tensor, error: Tensor) -> Tensor:
+        """l1 / bayesian / log_bayesian of (uncertainty, error) (reference :389-403)."""
+        return LT.nll(predicted, error, self.loss_type)
+
+    def forward(self, predicted: Tensor, image: Tensor, error: Tensor) -> Tensor:
+        """Reference :405-434 (F5: the consistency takes the uncertainty as
+        the compared map and the shift, the disparity as the sampled image)."""
+        if isinstance(self.pool, nn.AvgPool2d):
+            h, w = predicted.shape[-2:]
+            if h < 4 or w < 4:
+                raise ValueError(f'ReprojectionErrorLoss: pooling=True needs a level of at least '
+                                 f'4x4; got {h}x{w}')
+        error = error.detach()
+        predicted, image, error = self.pool(predicted), self.pool(image), self.pool(error)
+        disparity, uncertainty = torch.split(predicted, [2, 2], dim=1)
+        loss = self.loss_function(uncertainty, error)
+        if self.smoothness_weight > 0:
+            loss = loss + self.smoothness(uncertainty, image) * self.smoothness_weight
+        if self.consistency_weight > 0:
+            loss = loss + self.consistency(uncertainty, disparity) * self.consistency_weight
+        return loss
 
 
 class TukraUncertaintyLoss(nn.Module):
@@ -165,6 +224,28 @@ class TukraUncertaintyLoss(nn.Module):
                 'w_err': float(self.predictive_error_weight),
                 'pool': isinstance(pe.pool, nn.AvgPool2d)}
 
+    def _composed(self, image_pyramid, predictions, recon_pyramid):
+        """The reference's per-level loop (:539-550) over the standalone
+        modules, for a recon that is not reconstruct_pyramid's own output (an
+        occlusion-masked or blended one...): per level WSSIM 2 launches,
+        consistency 2, smoothness 2 and the error term up to 6 forward; the
+        gradients reach ``predictions`` and ``recon_pyramid``."""
+        wssim = cons = smooth = err = 0
+        for i, (images, prediction, recon) in enumerate(zip(image_pyramid, predictions,
+                                                            recon_pyramid)):
+            disparity = prediction[:, 0:2]
+            wssim = wssim + self.wssim(images, recon)
+            cons = cons + self.consistency(disparity)
+            smooth = smooth + self.smoothness(disparity, images) / (2 ** i)
+            err = err + self.predictive_error(prediction, images,
+                                              self.wssim.previous_image_error)
+        disp_loss = wssim * self.wssim_weight + cons * self.consistency_weight \
+            + smooth * self.smoothness_weight
+        error_loss = err * self.predictive_error_weight
+        terms = torch.stack([t.detach().float() for t in
+                             (disp_loss, error_loss, wssim, cons, smooth, err)])
+        return disp_loss, error_loss, terms
+
     def forward(self, image_pyramid: ImagePyramid, predictions: ImagePyramid,
                 recon_pyramid: ImagePyramid, epoch: Optional[int] = None,
                 discriminator: Optional[Module] = None):
@@ -179,20 +260,25 @@ class TukraUncertaintyLoss(nn.Module):
         ``epoch``, so one captured graph serves both sides of
         ``perceptual_start``.  gate 1.0 leaves the term's value and gradient
         bits unchanged; gate 0.0 makes them exact zeros (finite terms)."""
-        for p, im, r in zip(predictions, image_pyramid, recon_pyramid):
-            tag = getattr(r, '_umamd_recon', None)
-            if tag is None or tag != (id(p), id(im)):
-                raise ValueError('TukraUncertaintyLoss (umamd): recon_pyramid must be '
-                                 'train.utils.reconstruct_pyramid(predictions, image_pyramid) '
-                                 '(the fused kernels re-derive that warp and differentiate '
-                                 'through it)')
         pending = [r for r in recon_pyramid if getattr(r, '_umamd_pending', False)]
         if pending and len(pending) != len(recon_pyramid):
             raise ValueError('TukraUncertaintyLoss (umamd): partly deferred recon_pyramid')
-        disp_loss, error_loss, terms, emap = LF.tukra_loss(
-            self._cfg(), list(predictions), list(image_pyramid),
-            list(recon_pyramid) if pending else None)
-        self.wssim._previous_image_error = emap
+        tagged = all(getattr(r, '_umamd_recon', None) == (id(p), id(im))
+                     for p, im, r in zip(predictions, image_pyramid, recon_pyramid))
+        if tagged:
+            # the recon is reconstruct_pyramid(predictions, image_pyramid): the fused
+            # kernels re-derive that warp and differentiate through it
+            disp_loss, error_loss, terms, emap = LF.tukra_loss(
+                self._cfg(), list(predictions), list(image_pyramid),
+                list(recon_pyramid) if pending else None)
+            self.wssim._previous_image_error = emap
+        else:
+            if pending:
+                raise ValueError('TukraUncertaintyLoss (umamd): a deferred (unwritten) '
+                                 'recon_pyramid is only filled by the fused loss of the '
+                                 'predictions and images it was made from')
+            disp_loss, error_loss, terms = self._composed(image_pyramid, predictions,
+                                                          recon_pyramid)
         self.last_terms = terms  # [disp, error, wssim, consistency, smoothness, error-term]
         if discriminator is not None:
             # adversarial terms (reference :552-564); the recon pyramid carries

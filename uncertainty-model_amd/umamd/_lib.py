@@ -156,6 +156,18 @@ _SIG = {
     'um_loss_pool_bwd': (_I, [_I, _I, _I, _I, _P, _P, _F, _I, _F, _F, _F, _F, _F, _F, _P, _P, _P,
                               _P, _P, _P, 's']),
     'um_image_error': (_I, [_P, _P, _I, _I, _I, _F, _P, 's']),
+    'um_lossterm_ws': (_L, [_I, _I, _I]),
+    'um_image_error_k': (_I, [_P, _P, _I, _I, _I, _F, _F, _F, _P, _P, _P, 's']),
+    'um_image_error_bwd': (_I, [_P, _P, _I, _I, _I, _F, _F, _F, _I, _P, _P, _P, 's']),
+    'um_warp_bwd_img_max_cw': (_I, []),
+    'um_warp_bwd_img': (_I, [_P, _I, _I, _I, _I, _P, _L, _L, _F, _P, 's']),
+    'um_consistency_fwd': (_I, [_P, _L, _L, _L, _P, _L, _L, _L, _I, _I, _I, _P, _P, 's']),
+    'um_consistency_bwd': (_I, [_P, _L, _L, _L, _P, _L, _L, _L, _I, _I, _I, _P, _P, _P, _P, _I,
+                                's']),
+    'um_smoothness_fwd': (_I, [_P, _L, _L, _L, _P, _I, _I, _I, _P, _P, 's']),
+    'um_smoothness_bwd': (_I, [_P, _L, _L, _L, _P, _I, _I, _I, _P, _P, 's']),
+    'um_nll_fwd': (_I, [_P, _L, _L, _L, _P, _L, _L, _L, _I, _I, _I, _I, _P, _P, 's']),
+    'um_nll_bwd': (_I, [_P, _L, _L, _L, _P, _L, _L, _L, _I, _I, _I, _I, _P, _P, 's']),
     'um_nhwc_to_image': (_I, [_I, _P, _I, _I, _I, _I, _I, _P, 's']),
     'um_disc_head_fwd': (_I, [_I, _P, _I, _I, _I, _P, _P, _P, 's']),
     'um_disc_head_bwd': (_I, [_I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, 's']),

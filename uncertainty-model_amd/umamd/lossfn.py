@@ -1,7 +1,9 @@
 """Loss-stack autograd functions over the umamd C ABI.
 
   * ``scale_pyramid``       reference train/utils.py:27-50, every level in one launch
-  * ``reconstruct``         reference train/utils.py:65-97 (+ _left/_right 100-109)
+  * ``reconstruct``         reference train/utils.py:65-97 (+ _left/_right 100-109),
+                            differentiable w.r.t. the disparity (um_warp_bwd)
+                            and the sampled image (um_warp_bwd_img)
   * ``reconstruct_pyramid`` reference train/utils.py:112-135, one launch
   * ``tukra_loss``          reference train/loss.py:512-568 with the sub-losses
                             of loss.py:15-264,340-434: ONE forward launch over
@@ -114,21 +116,28 @@ class _WarpFn(torch.autograd.Function):
         ctx.save_for_backward(d, imgc)
         ctx.dshape = disp.shape
         ctx.ddtype = disp.dtype
+        ctx.idtype = img.dtype
         return out
 
     @staticmethod
     def backward(ctx, g):
-        if ctx.needs_input_grad[1]:
-            raise NotImplementedError('umamd reconstruct(): gradient w.r.t. the image (a data '
-                                      'tensor in every reference call site) is not implemented')
         d, imgc = ctx.saved_tensors
         N, C, H, W = imgc.shape
-        gd = torch.empty((N, 1, H, W), dtype=torch.float32, device=g.device)
         _, sn, sp = _disp_strides(d)
         gc = _f32c(g)  # keep alive until the launch is queued (no temporaries by pointer)
-        call('um_warp_bwd', ptr(imgc), N, C, H, W, d.data_ptr(), sn, sp, ctx.sign,
-             ptr(gc), ptr(gd), H * W, 1)
-        return gd.to(ctx.ddtype).reshape(ctx.dshape), None, None
+        gd = gimg = None
+        if ctx.needs_input_grad[0]:
+            gd = torch.empty((N, 1, H, W), dtype=torch.float32, device=g.device)
+            call('um_warp_bwd', ptr(imgc), N, C, H, W, d.data_ptr(), sn, sp, ctx.sign,
+                 ptr(gc), ptr(gd), H * W, 1)
+            gd = gd.to(ctx.ddtype).reshape(ctx.dshape)
+        if ctx.needs_input_grad[1]:
+            # the scatter through the four taps (every element stored once: no zeros needed)
+            gimg = torch.empty((N, C, H, W), dtype=torch.float32, device=g.device)
+            call('um_warp_bwd_img', ptr(gc), N, C, H, W, d.data_ptr(), sn, sp, ctx.sign,
+                 ptr(gimg))
+            gimg = gimg.to(ctx.idtype)
+        return gd, gimg, None
 
 
 def reconstruct(disparity: torch.Tensor, opposite_image: torch.Tensor, sign: float = 1.0):
