@@ -778,6 +778,48 @@ int um_depth_post(const float* pred, long pred_sn, long pred_sp, int N, int H, i
                   int Ws, const float* params, float* disparity, float* depth,
                   float* uncertainty, float* lr_error, unsigned char* valid,
                   hipStream_t stream);
+/* The display image (umamd/render.py, DepthPipeline(render=...)): a float map
+ * coloured through a 256-entry table and blended over the camera frame.
+ * Everything is per pixel over flat maps, count = N * Hs * Ws.
+ *
+ * um_depth_render: value f32 [count]; valid u8 [count] or NULL (all valid);
+ * frame u8 [count][3] RGB or NULL (black); lut u8 [256][3]; rparams DEVICE
+ * f32[4] = (lo, hi, opacity, invalid_opacity), read by the kernel, so a
+ * captured graph sees new values at its next replay; range DEVICE f32[2] or
+ * NULL, if given it replaces (lo, hi) (the output of um_value_range); rgb u8
+ * [count][3].  Every float step a separate f32 operation, IEEE division:
+ *   t   = (v - lo) / (hi - lo);  if inverse: t = 1 - t
+ *   s   = t * 256
+ *   c   = isnan(s) ? (0,0,0) : lut[s < 0 ? 0 : (int)min(s, 255)]   (truncates)
+ *   a   = q(valid[i] != 0 ? opacity : invalid_opacity),
+ *         q(x) = (int)(clamp(x, 0, 1) * 256 + 0.5), q(NaN) = 0
+ *   rgb = (c * a + frame[i] * (256 - a) + 128) >> 8       per channel, integer
+ * With lut = floor(cmap(arange(256))[:, :3] * 255 + 0.5) this is matplotlib's
+ * Colormap.__call__ on an f32 array (reference train/utils.py:177-199
+ * to_heatmap: below the range entry 0, s >= 256 entry 255, NaN black) followed
+ * by the x * 255 + 0.5 rounding of save_image; a = 256 returns c, a = 0 the
+ * frame.  One thread per 4 pixels (16-byte value load, dword mask, three
+ * dwords of frame and rgb; a scalar form for the tail and for bases that are
+ * not aligned: value 16, valid / frame / rgb 4), the table in LDS.
+ *
+ * um_value_range: range[0] = min, range[1] = max of value[i] over the pixels
+ * with valid[i] != 0 (NULL: every pixel) that are not NaN; +-inf take part;
+ * no such pixel: (+inf, -inf), which renders black.  Two launches (at most 256
+ * workgroup partials in ws, then one workgroup), no atomics and no state
+ * between calls: deterministic, safe to replay.  ws: um_value_range_ws(count)
+ * bytes (host query), 4-byte aligned.
+ * Measured inside DepthPipeline's graph (tools/bench_depth_render.py, MI355X,
+ * 1024x1280, B=1, medians of 3 alternated repeats): um_depth_render adds
+ * 0.0024 ms to the 1.1906 ms frame, um_value_range + um_depth_render 0.0172 ms;
+ * the same picture from torch device ops adds 0.247 ms, the host path
+ * (copy back, matplotlib, numpy) 27.6 ms.
+ * count <= 0 or a null value / lut / rparams / rgb / range / ws: UM_ERR_ARG. */
+long um_value_range_ws(long count);
+int um_value_range(const float* value, const unsigned char* valid, long count, float* range,
+                   void* ws, hipStream_t stream);
+int um_depth_render(const float* value, const unsigned char* valid, const unsigned char* frame,
+                    long count, const unsigned char* lut, const float* rparams,
+                    const float* range, int inverse, unsigned char* rgb, hipStream_t stream);
 
 /* ------------------------------------------------ SyncBN exchange (IPC) ---
  * SyncBatchNorm statistics exchanged device-side over IPC-mapped per-rank

@@ -13,11 +13,15 @@ adds both ends of the deployment path,
                   depth = focal x baseline / disparity, the upsampled
                   uncertainty, the left-right consistency error and the
                   validity mask (include/umamd.h "deployment")
+  -> um_depth_render  only with ``render=``: one of the maps coloured and
+                  blended over the frame, uint8 [B,Hs,Ws,3] (umamd/render.py;
+                  after um_value_range with ``render_range='auto'``)
 
 captured as ONE torch.cuda.CUDAGraph over static buffers.  ``__call__``
 copies the frames in and replays; it never synchronises with the host.  The
 calibration and the three thresholds live in a 4-float device block the kernel
-reads, so ``set_params`` needs no recapture.
+reads, so ``set_params`` needs no recapture; the display stage has a block of
+its own (range and opacities).
 """
 from __future__ import annotations
 
@@ -26,11 +30,36 @@ import math
 import torch
 
 from . import _lib as L
+from . import render as R
 from ._lib import call, ptr, query
 from .imageprep import resize_coeffs
 from .infer import InferenceEngine, _eval_mode
 
 PARAMS = ('focal_baseline', 'min_disparity', 'max_uncertainty', 'max_lr_error')
+RENDERS = ('disparity', 'depth', 'uncertainty', 'lr_error')
+
+
+def _check_render(render, colour_map, render_range, opacity, invalid_opacity):
+    """the display stage's arguments -> (table, (lo, hi) or None for 'auto',
+    opacity, invalid_opacity); raises before any GPU work"""
+    if not isinstance(render, str) or render not in RENDERS:
+        raise ValueError(f'DepthPipeline: render={render!r}: None or one of {RENDERS}')
+    table = R.lut(colour_map)
+    if isinstance(render_range, str):
+        if render_range != 'auto':
+            raise ValueError(f"DepthPipeline: render_range={render_range!r}: (lo, hi) or 'auto'")
+        rng = None
+    else:
+        try:
+            lo, hi = render_range
+        except (TypeError, ValueError):
+            raise ValueError(f"DepthPipeline: render_range={render_range!r}: (lo, hi) or "
+                             f"'auto'") from None
+        rng = R.check_range(lo, hi, 'DepthPipeline: render_range')
+        if rng is None:
+            raise ValueError("DepthPipeline: render_range=(None, None): (lo, hi) or 'auto'")
+    return table, rng, R.check_number('DepthPipeline: opacity', opacity), \
+        R.check_number('DepthPipeline: invalid_opacity', invalid_opacity)
 
 
 def _check_frames(frames, shape):
@@ -65,12 +94,28 @@ class DepthPipeline:
     ``set_params`` changes any of the four without recapture.  ``refresh()``
     must be called after the model's weights or running statistics changed.
     ``fused`` is the InferenceEngine's switch; ``capture=False`` runs the same
-    three stages eagerly."""
+    three stages eagerly.
+
+    ``render='disparity' | 'depth' | 'uncertainty' | 'lr_error'`` adds a
+    display stage to the same graph: ``out['render']``, uint8 [B,Hs,Ws,3], is
+    that map coloured through ``colour_map`` (a name or a uint8 [256, 3]
+    table, ``umamd.render.lut``) over ``render_range=(lo, hi)`` -- or
+    ``'auto'``, the min and max over the valid pixels of the batch, per call
+    -- ``1 -`` that if ``inverse``, blended over the input frame with
+    ``opacity`` where ``valid`` and ``invalid_opacity`` elsewhere (0: the
+    camera image shows through).  ``set_params`` then also takes
+    ``render_lo``, ``render_hi`` (not with ``'auto'``), ``opacity`` and
+    ``invalid_opacity``.  With ``render=None`` (the default) nothing of this
+    is allocated, launched or returned."""
 
     def __init__(self, model, src_height: int, src_width: int, batch: int = 1, height: int = 256,
                  width: int = 512, scale: float = 1.0, focal_baseline: float = 1.0,
                  min_disparity: float = 1e-3, max_uncertainty: float = math.inf,
-                 max_lr_error: float = math.inf, fused: bool = True, capture: bool = True):
+                 max_lr_error: float = math.inf, fused: bool = True, capture: bool = True,
+                 render=None, colour_map='inferno', render_range='auto', opacity: float = 1.0,
+                 invalid_opacity: float = 0.0, inverse: bool = False):
+        rcfg = None if render is None else _check_render(render, colour_map, render_range,
+                                                         opacity, invalid_opacity)
         B, H, W, Hs, Ws = int(batch), int(height), int(width), int(src_height), int(src_width)
         if H <= 0 or W <= 0 or H % 32 or W % 32:
             raise ValueError(f'image size {H}x{W}: height and width must be multiples of 32')
@@ -108,6 +153,22 @@ class DepthPipeline:
                        'max_uncertainty': float(max_uncertainty),
                        'max_lr_error': float(max_lr_error)}
         self._params = torch.tensor([self.params[k] for k in PARAMS], **f32)
+        self.render = render
+        if rcfg is not None:
+            table, rng, op, iop = rcfg
+            self.inverse = bool(inverse)
+            self.render_auto = rng is None
+            lo, hi = rng or (0.0, 1.0)  # 'auto': replaced by the device range
+            self.render_params = {'render_lo': lo, 'render_hi': hi, 'opacity': op,
+                                  'invalid_opacity': iop}
+            self._rparams = torch.tensor([self.render_params[k] for k in R.RENDER_PARAMS], **f32)
+            self._lut = table.to(dev)
+            self._render = torch.zeros((B, Hs, Ws, 3), dtype=torch.uint8, device=dev)
+            self._range = self._range_ws = None
+            if self.render_auto:
+                self._range = torch.zeros(2, **f32)
+                self._range_ws = torch.zeros(query('um_value_range_ws', B * Hs * Ws),
+                                             dtype=torch.uint8, device=dev)
         self._graph = None
         self._out = None
         self._called = False
@@ -129,6 +190,13 @@ class DepthPipeline:
         call('um_depth_post', ptr(out), out.stride(0), out.stride(2), B, H, W, Hs, Ws,
              ptr(self._params), ptr(self._disparity), ptr(self._depth), ptr(self._uncertainty),
              ptr(self._lr_error), ptr(self._valid))
+        if self.render is not None:
+            value = getattr(self, '_' + self.render)
+            if self.render_auto:
+                R.value_range(value, self._valid, out=self._range, ws=self._range_ws)
+            call('um_depth_render', ptr(value), ptr(self._valid), ptr(self._frames), B * Hs * Ws,
+                 ptr(self._lut), ptr(self._rparams), ptr(self._range), int(self.inverse),
+                 ptr(self._render))
         return out
 
     def _capture(self):
@@ -156,13 +224,30 @@ class DepthPipeline:
                 self._capture()
 
     def set_params(self, **kw):
-        """any of focal_baseline, min_disparity, max_uncertainty, max_lr_error:
-        written into the device block in place, seen by the next call"""
-        bad = sorted(set(kw) - set(PARAMS))
+        """any of focal_baseline, min_disparity, max_uncertainty, max_lr_error
+        and, with ``render=``, render_lo, render_hi (a fixed range only),
+        opacity, invalid_opacity: written into the device blocks in place,
+        seen by the next call"""
+        known = PARAMS + (R.RENDER_PARAMS if self.render is not None else ())
+        bad = sorted(set(kw) - set(known))
         if bad:
-            raise TypeError(f'DepthPipeline.set_params: unknown {bad}; one of {PARAMS}')
-        self.params.update({k: float(v) for k, v in kw.items()})
-        self._params.copy_(torch.tensor([self.params[k] for k in PARAMS], dtype=torch.float32))
+            raise TypeError(f'DepthPipeline.set_params: unknown {bad}; one of {known}')
+        rkw = {k: kw.pop(k) for k in R.RENDER_PARAMS if k in kw}
+        if rkw:
+            fixed = [k for k in ('render_lo', 'render_hi') if k in rkw]
+            if fixed and self.render_auto:
+                raise ValueError(f"DepthPipeline.set_params: {fixed} on a pipeline built with "
+                                 f"render_range='auto' (the range is found per call)")
+            rkw = {k: R.check_number(f'DepthPipeline.set_params: {k}', v)
+                   for k, v in rkw.items()}
+        if kw:
+            self.params.update({k: float(v) for k, v in kw.items()})
+            self._params.copy_(torch.tensor([self.params[k] for k in PARAMS],
+                                            dtype=torch.float32))
+        if rkw:
+            self.render_params.update(rkw)
+            self._rparams.copy_(torch.tensor([self.render_params[k] for k in R.RENDER_PARAMS],
+                                             dtype=torch.float32))
 
     def __call__(self, frames: torch.Tensor):
         _check_frames(frames, self.src_shape)
@@ -180,7 +265,10 @@ class DepthPipeline:
         """views of the static buffers of the last call (valid until the next one)"""
         if not self._called:
             raise L.UmamdError('DepthPipeline.last() before the first call')
-        return {'disparity': self._disparity, 'depth': self._depth,
-                'uncertainty': self._uncertainty, 'lr_error': self._lr_error,
-                'valid': self._valid.view(torch.bool),
-                'prediction': self._out.permute(0, 3, 1, 2)[:, :4]}
+        out = {'disparity': self._disparity, 'depth': self._depth,
+               'uncertainty': self._uncertainty, 'lr_error': self._lr_error,
+               'valid': self._valid.view(torch.bool),
+               'prediction': self._out.permute(0, 3, 1, 2)[:, :4]}
+        if self.render is not None:
+            out['render'] = self._render
+        return out
