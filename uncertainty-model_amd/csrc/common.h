@@ -198,6 +198,19 @@ __device__ __forceinline__ int reflect_idx(int i, int n) {
   return i;
 }
 
+// torch upsample_bilinear2d(align_corners=True), in -> out: the two source
+// indices of output index i and the weight of the second.  deploy.hip compiles
+// this with FMA contraction off (its pragma stands before this include) so
+// that um_depth_post rounds l1 as a multiply and a subtraction; keep it so.
+__device__ __forceinline__ void up_index(int i, int in, int out, int& i0, int& i1, float& l1) {
+  const float sc = out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f;
+  const float src = sc * (float)i;
+  i0 = (int)src;
+  if (i0 > in - 1) i0 = in - 1;
+  i1 = i0 + ((i0 < in - 1) ? 1 : 0);
+  l1 = src - (float)i0;
+}
+
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 
 // Arrival on an agent-scope counter shared by `expected` workgroups (the

@@ -30,16 +30,6 @@ struct CatArgs {
   int nsrc;
 };
 
-// torch upsample_bilinear2d(align_corners=True) source index for output i
-__device__ __forceinline__ void up_index(int i, int in, int out, int& i0, int& i1, float& l1) {
-  const float sc = out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f;
-  const float src = sc * (float)i;
-  i0 = (int)src;
-  if (i0 > in - 1) i0 = in - 1;
-  i1 = i0 + ((i0 < in - 1) ? 1 : 0);
-  l1 = src - (float)i0;
-}
-
 __device__ __forceinline__ float ld_any(const void* p, long off, int dt) {
   return dt == UM_BF16 ? __bfloat162float(reinterpret_cast<const bf16_t*>(p)[off])
                        : reinterpret_cast<const float*>(p)[off];

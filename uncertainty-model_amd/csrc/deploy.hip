@@ -13,9 +13,17 @@
 //                   ConsistencyLoss, train/loss.py:179-185, with the warp of
 //                   train/utils.py:65-103), the align_corners=True upsample
 //                   (loss.py:120-121), pixels, depth and the validity mask.
-#include "common.h"
-
+#include <hip/hip_runtime.h>
 #include <limits.h>
+
+// No FMA contraction in this file's own code or in the helpers it takes from
+// common.h (up_index), every fused multiply-add is written out: the aligned
+// and the unaligned form of depth_post_kernel (and any later variant) then
+// round alike and agree bit for bit, instead of by whichever fusion each
+// instantiation happened to get.  (frame_prep_kernel is integer arithmetic.)
+#pragma clang fp contract(off)
+
+#include "common.h"
 
 namespace {
 
@@ -107,12 +115,8 @@ frame_prep_kernel(const uint8_t* __restrict__ src, int Hs, int Ws, int Hd, int W
 }
 
 // ---------------------------------------------------------- depth post ----
-// No FMA contraction below, every fused multiply-add is written out: the
-// aligned and the unaligned form of the kernel (and any later variant) then
-// round alike and agree bit for bit, instead of by whichever fusion each
-// instantiation happened to get.
-#pragma clang fp contract(off)
-
+// (contraction is off, see the top of the file: the fused multiply-adds below
+// are the written ones)
 struct PostArgs {
   const float* pred;
   long sn, sp;
@@ -121,16 +125,6 @@ struct PostArgs {
   float *disparity, *depth, *uncertainty, *lr_error;
   uint8_t* valid;
 };
-
-// F.interpolate(bilinear, align_corners=True) source index and weight
-__device__ __forceinline__ void up_index(int i, int in, int out, int& i0, int& i1, float& l1) {
-  const float sc = (float)(in - 1) / (float)(out - 1);
-  const float src = sc * (float)i;
-  i0 = (int)src;
-  if (i0 > in - 1) i0 = in - 1;
-  i1 = i0 + ((i0 < in - 1) ? 1 : 0);
-  l1 = src - (float)i0;
-}
 
 // torch.linspace(0, 1, n) in f32 (CPU kernel: symmetric halves), n >= 2
 __device__ __forceinline__ float lin01(int i, int n) {

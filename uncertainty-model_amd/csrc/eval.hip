@@ -32,6 +32,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "common.h"
+#include "lossdev.h"
 
 namespace {
 
@@ -179,51 +180,18 @@ __global__ void spars_mean_kernel(const double* norm, int nseg, int steps, float
 }
 
 // ------------------------------------------------------ fused eval maps ----
-// The warp / 3x3-SSIM / upsample helpers below are this file's own copies of
-// the ones in loss.hip (warp_at, sample, win_stats, ssim_of, up_index), kept
-// here so the training kernels' translation unit does not change.
-__device__ __forceinline__ float lin01(int i, int n) {
-  // torch.linspace(0, 1, n) (CPU kernel: symmetric halves)
-  if (n <= 1) return 0.f;
-  const float step = 1.f / (float)(n - 1);
-  return (i < n / 2) ? step * (float)i : 1.f - step * (float)(n - 1 - i);
-}
-
-__device__ __forceinline__ float pv(const float* p, int y, int x, int H, int W) {
-  return (x >= 0 && x < W && y >= 0 && y < H) ? p[(long)y * W + x] : 0.f;
-}
-
-// grid_sample(bilinear, zeros) of plane p at the linspace grid shifted by
-// `shift` along x (reference train/utils.py:77-97)
-__device__ __forceinline__ float warp_sample(const float* p, int x, int y, float shift, int W,
-                                             int H) {
-  const float gx = 2.f * (lin01(x, W) + shift) - 1.f;
-  const float gy = 2.f * lin01(y, H) - 1.f;
-  const float ix = (gx + 1.f) * ((float)W * 0.5f) - 0.5f;
-  const float iy = (gy + 1.f) * ((float)H * 0.5f) - 0.5f;
-  const float fx = floorf(ix), fy = floorf(iy);
-  const int x0 = (int)fx, y0 = (int)fy;
-  const float w = ix - fx, e = 1.f - w, n = iy - fy, s = 1.f - n;
-  const float nw = pv(p, y0, x0, H, W), ne = pv(p, y0, x0 + 1, H, W);
-  const float sw = pv(p, y0 + 1, x0, H, W), se = pv(p, y0 + 1, x0 + 1, H, W);
-  return nw * (s * e) + ne * (s * w) + sw * (n * e) + se * (n * w);
-}
-
-__device__ __forceinline__ void up_index(int i, int in, int out, int& i0, int& i1, float& l1) {
-  const float sc = out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f;
-  const float src = sc * (float)i;
-  i0 = (int)src;
-  if (i0 > in - 1) i0 = in - 1;
-  i1 = i0 + ((i0 < in - 1) ? 1 : 0);
-  l1 = src - (float)i0;
-}
-
+// The reconstruction and the grid-to-pixel upsample are the loss kernels' own
+// helpers (lossdev.h: warp_at, sample, up_tap, dssim_up).
 constexpr int MTY = 16, MTX = 64;                    // pixel tile of one workgroup
 constexpr int MRY = MTY + 2 * SR, MRX = MTX + 2 * SR;  // staged: tile + gaussian halo
-constexpr int MGY = MTY + 3, MGX = MTX + 3;          // 3x3-SSIM grid points of the tile
+constexpr int MGY = Tile<MTY, MTX>::GY, MGX = Tile<MTY, MTX>::GX;  // 3x3-SSIM grid points
 constexpr int MG0 = SR - 2;  // staged row / column of grid point 0 (pixel tile origin - 2)
 
-// SSIM of the 3x3 window whose top-left is staged (r, q) (train/loss.py:43-74)
+// SSIM of the 3x3 window whose top-left is staged (r, q) (train/loss.py:43-74).
+// The same arithmetic as ssim_of(win_stats()) of lossdev.h, written out here:
+// which multiply-adds the compiler fuses depends on the shape of the code
+// around them, that call gives other last bits in this kernel than this form,
+// and the error map is kept bit-stable.
 __device__ __forceinline__ float ssim3(const float (*I)[MRX], const float (*R)[MRX], int r,
                                        int q) {
   constexpr float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f, k9 = 1.f / 9.f;
@@ -258,7 +226,7 @@ struct MapsArgs {
 //   * the gaussian SSIM of every full 11x11 window centred in the tile
 //     (separable, as ssim_gauss_kernel), summed in f64 into parts;
 //   * the 3x3 SSIM dissimilarity on the tile's grid points, summed over the
-//     channels in LDS (as image_error_kernel);
+//     channels in LDS (as lt_image_error_kernel of lossterms.hip);
 // and finally upsamples the dissimilarity grid to the tile's pixels.
 __global__ void __launch_bounds__(256) eval_maps_kernel(MapsArgs a) {
   __shared__ float sI[MRY][MRX], sR[MRY][MRX];
@@ -288,7 +256,7 @@ __global__ void __launch_bounds__(256) eval_maps_kernel(MapsArgs a) {
       if (y >= 0 && y < H && x >= 0 && x < W) {
         const long o = (long)y * W + x;
         iv = view[c * HW + o];
-        rv = warp_sample(opp + c * HW, x, y, sign * disp[o * a.psp], W, H);
+        rv = sample(opp + c * HW, warp_at(x, y, sign * disp[o * a.psp], W, H), H, W, 1, nullptr);
         if (a.recon != nullptr && r >= SR && r < SR + MTY && q >= SR && q < SR + MTX)
           a.recon[((long)n * 6 + v * 3 + c) * HW + o] = rv;
       }
@@ -346,16 +314,8 @@ __global__ void __launch_bounds__(256) eval_maps_kernel(MapsArgs a) {
     const int ly = i / MTX, lx = i % MTX;
     const int y = ty0 + ly, x = tx0 + lx;
     if (y >= H || x >= W) continue;
-    int y0, y1, x0, x1;
-    float wy, wx;
-    up_index(y, gh, H, y0, y1, wy);
-    up_index(x, gw, W, x0, x1, wx);
-    // y0 >= y - 2 up to the rounding of the scale: keep the index in the tile
-    const int r0 = max(y0 - (ty0 - 2), 0), r1 = max(y1 - (ty0 - 2), 0);
-    const int q0 = max(x0 - (tx0 - 2), 0), q1 = max(x1 - (tx0 - 2), 0);
     a.err[((long)n * 2 + v) * HW + (long)y * W + x] =
-        (1.f - wy) * ((1.f - wx) * sD[r0][q0] + wx * sD[r0][q1]) +
-        wy * ((1.f - wx) * sD[r1][q0] + wx * sD[r1][q1]);
+        dssim_up<MGX>(sD, up_tap(y, H, ty0 - 2), up_tap(x, W, tx0 - 2));
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);

@@ -80,38 +80,6 @@ __device__ float up_adj_sum(int j, int in, int out) {
 constexpr float C1 = 0.01f * 0.01f;
 constexpr float C2 = 0.03f * 0.03f;
 
-// SSIM of one channel over the 3x3 window whose top-left is (r, q) of the
-// staged tiles (reference train/loss.py:43-74: valid 3x3 average pools)
-struct Stats {
-  float mx, my, vx, vy, vxy;
-};
-template <int RX>
-__device__ __forceinline__ Stats win_stats(const float (*I)[RX], const float (*R)[RX], int r,
-                                           int q) {
-  float sx = 0, sy = 0, sxx = 0, syy = 0, sxy = 0;
-#pragma unroll
-  for (int u = 0; u < 3; ++u)
-#pragma unroll
-    for (int w = 0; w < 3; ++w) {
-      const float xv = I[r + u][q + w], yv = R[r + u][q + w];
-      sx += xv; sy += yv; sxx += xv * xv; syy += yv * yv; sxy += xv * yv;
-    }
-  // the 3x3 mean as a multiply by 1/9 (within an ulp of the reference's
-  // avg_pool division; an IEEE division here is ~10 instructions)
-  constexpr float k9 = 1.f / 9.f;
-  Stats st;
-  st.mx = sx * k9;
-  st.my = sy * k9;
-  st.vx = sxx * k9 - st.mx * st.mx;
-  st.vy = syy * k9 - st.my * st.my;
-  st.vxy = sxy * k9 - st.mx * st.my;
-  return st;
-}
-__device__ __forceinline__ float ssim_of(const Stats& t) {
-  return ((2 * t.mx * t.my + C1) * (2 * t.vxy + C2)) /
-         ((t.mx * t.mx + t.my * t.my + C1) * (t.vx + t.vy + C2));
-}
-
 // ----------------------------------------------------------------- pyramid --
 struct PyrArgs {
   const float* x;
@@ -291,19 +259,10 @@ __device__ __forceinline__ LScale scale_desc(const LArgs& a, int s) {
 
 
 // ---------------------------------------------------------- tile staging --
-// A tile of TY x TX pixels of one image, scale and view.  Staged region =
-// rows [ty0-2, ty0+TY+3), cols [tx0-2, tx0+TX+3): the pixels, the SSIM
-// windows of the DSSIM grid points the tile's upsample reads (grid rows
-// [ty0-2, ty0+TY]) and the smoothness neighbours.  Out-of-image positions
-// hold zeros.  Loads are issued in groups of G independent positions
-// (branch-free: clamped addresses, selects), so each thread keeps ~G*15
-// loads in flight instead of one dependent chain at a time.
-template <int TY, int TX>
-struct Tile {
-  static constexpr int RY = TY + 5, RX = TX + 5;  // staged region
-  static constexpr int GY = TY + 3, GX = TX + 3;  // grid points
-  static constexpr int NP = RY * RX;
-};
+// A Tile<TY, TX> (lossdev.h) of one image, scale and view.  Out-of-image
+// positions of the staged region hold zeros.  Loads are issued in groups of
+// G independent positions (branch-free: clamped addresses, selects), so each
+// thread keeps ~G*15 loads in flight instead of one dependent chain at a time.
 
 __device__ __forceinline__ float ldc(const float* p, int y, int x, int H, int W, int st) {
   // plane value at (y, x), zero outside (address clamped: no branch)
@@ -329,10 +288,6 @@ __device__ __forceinline__ void ldc2(const float* p, int y, int x, int H, int W,
 // per-tile coordinate tables (LDS): lin01 of the staged columns, the warp's
 // row part of the staged rows, and the DSSIM upsample taps of the pixel rows
 // and columns (relative to the grid tile origin ty0-2 / tx0-2)
-struct UpTap {
-  int i0, i1;
-  float l1;
-};
 template <int TY, int TX>
 struct Tabs {
   float lin[Tile<TY, TX>::RX];
@@ -475,14 +430,6 @@ __device__ __forceinline__ void cons_samples(const float* opp, int H, int W, con
             tp[k][3] * (u.n * u.w);
     if (dix) dix[k] = u.s * (tp[k][1] - tp[k][0]) + u.n * (tp[k][3] - tp[k][2]);
   }
-}
-
-// DSSIM upsampled to pixel (ly, lx) of the tile from the grid tile
-template <int GX>
-__device__ __forceinline__ float dssim_up(const float (*sD)[GX], const UpTap& uy,
-                                          const UpTap& ux) {
-  return (1.f - uy.l1) * ((1.f - ux.l1) * sD[uy.i0][ux.i0] + ux.l1 * sD[uy.i0][ux.i1]) +
-         uy.l1 * ((1.f - ux.l1) * sD[uy.i1][ux.i0] + ux.l1 * sD[uy.i1][ux.i1]);
 }
 
 // Block sums of the six loss terms (f64) into parts[blockIdx.x][0..5]; a
@@ -1025,7 +972,11 @@ constexpr int ETY = 16, ETX = 64;
 using ET = Tile<ETY, ETX>;
 
 // WeightedSSIMLoss.image_error with an explicit recon (evaluation,
-// reference train/evaluate.py:151 -> train/loss.py:96-131): out [N][2][H][W]
+// reference train/evaluate.py:151 -> train/loss.py:96-131): out [N][2][H][W].
+// The same arithmetic as lt_image_error_kernel (lossterms.hip), kept as a
+// kernel of its own with its upsample written out: the compiler fuses the
+// multiply-adds of the two differently, their maps differ in the last bit or
+// two, and evaluation's error map keeps its bits.
 __global__ void __launch_bounds__(256) image_error_kernel(const float* __restrict__ img,
                                                           const float* __restrict__ rec, int N,
                                                           int H, int W, float alpha,
@@ -1060,7 +1011,7 @@ __global__ void __launch_bounds__(256) image_error_kernel(const float* __restric
       if (gy >= 0 && gy < gh && gx >= 0 && gx < gw) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-          const float ss = ssim_of(win_stats<ET::RX>(sI[c], sR[c], r, q));
+          const float ss = ssim_of(win_stats<ET::RX>(sI[c], sR[c], r, q), C1, C2);
           dv += fminf(fmaxf((1.f - ss) * 0.5f, 0.f), 1.f);
         }
         dv /= 3.f;

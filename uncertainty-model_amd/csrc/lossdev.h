@@ -1,6 +1,11 @@
-// Device helpers shared by the loss kernels (loss.hip, lossterms.hip): the
-// reference's linspace grid and bilinear warp (train/utils.py:65-97) and the
-// align_corners resize index (F.interpolate, train/loss.py:120).
+// Device helpers shared by the kernels that evaluate the reference's loss
+// arithmetic -- loss.hip (the fused training loss), lossterms.hip (the
+// standalone terms) and eval.hip (the evaluation engine's maps):
+//   * the linspace grid and bilinear warp of train/utils.py:65-97;
+//   * the 3x3 SSIM window of train/loss.py:43-74;
+//   * the tile geometry and the grid-to-pixel upsample of the DSSIM map
+//     (F.interpolate align_corners, train/loss.py:120; up_index itself is in
+//     common.h).
 #pragma once
 
 #include "common.h"
@@ -49,15 +54,6 @@ __device__ __forceinline__ float sample(const float* p, const Samp& t, int H, in
   return nw * (t.s * t.e) + ne * (t.s * t.w) + sw * (t.n * t.e) + se * (t.n * t.w);
 }
 
-__device__ __forceinline__ void up_index(int i, int in, int out, int& i0, int& i1, float& l1) {
-  const float sc = out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f;
-  const float src = sc * (float)i;
-  i0 = (int)src;
-  if (i0 > in - 1) i0 = in - 1;
-  i1 = i0 + ((i0 < in - 1) ? 1 : 0);
-  l1 = src - (float)i0;
-}
-
 __device__ __forceinline__ float sgnf(float x) { return (x > 0.f) - (x < 0.f); }
 
 // The same warp with the per-image constants hoisted: lin01 with a
@@ -91,6 +87,75 @@ __device__ __forceinline__ Samp warp_tab(float linx, const RowW& rw, float shift
   t.n = rw.n;
   t.s = 1.f - rw.n;
   return t;
+}
+
+// --------------------------------------------------------- 3x3 SSIM window --
+// Moments of one channel over the 3x3 window whose top-left is (r, q) of the
+// staged tiles (reference train/loss.py:43-74: valid 3x3 average pools)
+struct Stats {
+  float mx, my, vx, vy, vxy;
+};
+template <int RX>
+__device__ __forceinline__ Stats win_stats(const float (*I)[RX], const float (*R)[RX], int r,
+                                           int q) {
+  float sx = 0, sy = 0, sxx = 0, syy = 0, sxy = 0;
+#pragma unroll
+  for (int u = 0; u < 3; ++u)
+#pragma unroll
+    for (int w = 0; w < 3; ++w) {
+      const float xv = I[r + u][q + w], yv = R[r + u][q + w];
+      sx += xv; sy += yv; sxx += xv * xv; syy += yv * yv; sxy += xv * yv;
+    }
+  // the 3x3 mean as a multiply by 1/9 (within an ulp of the reference's
+  // avg_pool division; an IEEE division here is ~10 instructions)
+  constexpr float k9 = 1.f / 9.f;
+  Stats st;
+  st.mx = sx * k9;
+  st.my = sy * k9;
+  st.vx = sxx * k9 - st.mx * st.mx;
+  st.vy = syy * k9 - st.my * st.my;
+  st.vxy = sxy * k9 - st.mx * st.my;
+  return st;
+}
+__device__ __forceinline__ float ssim_of(const Stats& t, float c1, float c2) {
+  return ((2 * t.mx * t.my + c1) * (2 * t.vxy + c2)) /
+         ((t.mx * t.mx + t.my * t.my + c1) * (t.vx + t.vy + c2));
+}
+
+// ------------------------------------------------------------------ tiles --
+// A tile of TY x TX pixels: the staged region is rows [ty0-2, ty0+TY+3),
+// cols [tx0-2, tx0+TX+3) (the pixels, the SSIM windows of the DSSIM grid
+// points the tile's upsample reads and the smoothness neighbours), the grid
+// points are rows [ty0-2, ty0+TY+1), cols [tx0-2, tx0+TX+1)
+template <int TY, int TX>
+struct Tile {
+  static constexpr int RY = TY + 5, RX = TX + 5;  // staged region
+  static constexpr int GY = TY + 3, GX = TX + 3;  // grid points
+  static constexpr int NP = RY * RX;
+};
+
+// the two DSSIM grid taps of a pixel row or column, as indices into the
+// tile's grid (grid point g0 = tile origin - 2 is index 0)
+struct UpTap {
+  int i0, i1;
+  float l1;
+};
+// taps of pixel i of the upsample n - 2 -> n.  The clamp at 0 never changes a
+// value (int(sc * i) >= i - 2 for every i < n, 3 <= n <= 8192, in f32); it
+// keeps the LDS index non-negative whatever the rounding of the scale.
+__device__ __forceinline__ UpTap up_tap(int i, int n, int g0) {
+  UpTap u;
+  up_index(i, n - 2, n, u.i0, u.i1, u.l1);
+  u.i0 = max(u.i0 - g0, 0);
+  u.i1 = max(u.i1 - g0, 0);
+  return u;
+}
+// DSSIM upsampled to a pixel of the tile from the grid tile
+template <int GX>
+__device__ __forceinline__ float dssim_up(const float (*sD)[GX], const UpTap& uy,
+                                          const UpTap& ux) {
+  return (1.f - uy.l1) * ((1.f - ux.l1) * sD[uy.i0][ux.i0] + ux.l1 * sD[uy.i0][ux.i1]) +
+         uy.l1 * ((1.f - ux.l1) * sD[uy.i1][ux.i0] + ux.l1 * sD[uy.i1][ux.i1]);
 }
 
 }  // namespace

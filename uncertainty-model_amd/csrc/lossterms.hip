@@ -67,41 +67,17 @@ __global__ void __launch_bounds__(LNT) lt_finish_kernel(const double* __restrict
 }
 
 // --------------------------------------------------------- image error ------
-struct Win {
-  float mx, my, vx, vy, vxy;
-};
-// moments of the 3x3 window whose top-left is (r, q) of the staged tiles
-template <int RX>
-__device__ __forceinline__ Win win_of(const float (*X)[RX], const float (*Y)[RX], int r, int q) {
-  float sx = 0, sy = 0, sxx = 0, syy = 0, sxy = 0;
-#pragma unroll
-  for (int u = 0; u < 3; ++u)
-#pragma unroll
-    for (int w = 0; w < 3; ++w) {
-      const float xv = X[r + u][q + w], yv = Y[r + u][q + w];
-      sx += xv; sy += yv; sxx += xv * xv; syy += yv * yv; sxy += xv * yv;
-    }
-  constexpr float k9 = 1.f / 9.f;
-  Win t;
-  t.mx = sx * k9;
-  t.my = sy * k9;
-  t.vx = sxx * k9 - t.mx * t.mx;
-  t.vy = syy * k9 - t.my * t.my;
-  t.vxy = sxy * k9 - t.mx * t.my;
-  return t;
-}
+using ET = Tile<LTY, LTX>;
 
-constexpr int ERY = LTY + 5, ERX = LTX + 5;  // staged pixels: rows [ty0-2, ty0+TY+3)
-constexpr int EGY = LTY + 3, EGX = LTX + 3;  // SSIM grid cells: rows [ty0-2, ty0+TY+1)
-
-// out[n][v][y][x] = alpha * up(mean_c dssim_c) + (1 - alpha) * mean_c |I - R|;
+// WeightedSSIMLoss.image_error of an explicit recon: out[n][v][y][x] =
+// alpha * up(mean_c dssim_c) + (1 - alpha) * mean_c |I - R|;
 // parts (optional): the workgroup's sum of both views
 __global__ void __launch_bounds__(LNT) lt_image_error_kernel(
     const float* __restrict__ img, const float* __restrict__ rec, int N, int H, int W, float alpha,
     float c1, float c2, float* __restrict__ out, double* __restrict__ parts, int tiles_x,
     int tiles_y) {
-  __shared__ float sI[3][ERY][ERX], sR[3][ERY][ERX];
-  __shared__ float sD[EGY][EGX];
+  __shared__ float sI[3][ET::RY][ET::RX], sR[3][ET::RY][ET::RX];
+  __shared__ float sD[ET::GY][ET::GX];
   const int tid = threadIdx.x;
   const long HW = (long)H * W;
   const int per = tiles_x * tiles_y;
@@ -112,8 +88,8 @@ __global__ void __launch_bounds__(LNT) lt_image_error_kernel(
   for (int v = 0; v < 2; ++v) {
     const float* Iv = img + ((long)n * 6 + v * 3) * HW;
     const float* Rv = rec + ((long)n * 6 + v * 3) * HW;
-    for (int i = tid; i < ERY * ERX; i += LNT) {
-      const int r = i / ERX, q = i - r * ERX;
+    for (int i = tid; i < ET::RY * ET::RX; i += LNT) {
+      const int r = i / ET::RX, q = i - r * ET::RX;
       const int y = ty0 - 2 + r, x = tx0 - 2 + q;
       const bool in = y >= 0 && y < H && x >= 0 && x < W;
 #pragma unroll
@@ -123,16 +99,14 @@ __global__ void __launch_bounds__(LNT) lt_image_error_kernel(
       }
     }
     __syncthreads();
-    for (int i = tid; i < EGY * EGX; i += LNT) {
-      const int r = i / EGX, q = i - r * EGX;
+    for (int i = tid; i < ET::GY * ET::GX; i += LNT) {
+      const int r = i / ET::GX, q = i - r * ET::GX;
       const int gy = ty0 - 2 + r, gx = tx0 - 2 + q;
       float dv = 0.f;
       if (gy >= 0 && gy < gh && gx >= 0 && gx < gw) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-          const Win s = win_of<ERX>(sI[c], sR[c], r, q);
-          const float ss = ((2 * s.mx * s.my + c1) * (2 * s.vxy + c2)) /
-                           ((s.mx * s.mx + s.my * s.my + c1) * (s.vx + s.vy + c2));
+          const float ss = ssim_of(win_stats<ET::RX>(sI[c], sR[c], r, q), c1, c2);
           dv += fminf(fmaxf((1.f - ss) * 0.5f, 0.f), 1.f);
         }
         dv /= 3.f;
@@ -144,14 +118,7 @@ __global__ void __launch_bounds__(LNT) lt_image_error_kernel(
       const int ly = i / LTX, lx = i - ly * LTX;
       const int y = ty0 + ly, x = tx0 + lx;
       if (y >= H || x >= W) continue;
-      int y0, y1, x0, x1;
-      float wy, wx_;
-      up_index(y, gh, H, y0, y1, wy);
-      up_index(x, gw, W, x0, x1, wx_);
-      const int r0 = y0 - (ty0 - 2), r1 = y1 - (ty0 - 2);
-      const int q0 = x0 - (tx0 - 2), q1 = x1 - (tx0 - 2);
-      const float up = (1.f - wy) * ((1.f - wx_) * sD[r0][q0] + wx_ * sD[r0][q1]) +
-                       wy * ((1.f - wx_) * sD[r1][q0] + wx_ * sD[r1][q1]);
+      const float up = dssim_up<ET::GX>(sD, up_tap(y, H, ty0 - 2), up_tap(x, W, tx0 - 2));
       float l1 = 0.f;
 #pragma unroll
       for (int c = 0; c < 3; ++c) l1 += fabsf(sI[c][ly + 2][lx + 2] - sR[c][ly + 2][lx + 2]);
@@ -239,7 +206,7 @@ __global__ void __launch_bounds__(LNT) lt_image_error_bwd_kernel(
           G += wy[a] * wx[b] * gv;
         }
       }
-      const Win s = win_of<BRX>(sX, sY, r, q);
+      const Stats s = win_stats<BRX>(sX, sY, r, q);
       const float A = 2 * s.mx * s.my + c1, B = 2 * s.vxy + c2;
       const float C = s.mx * s.mx + s.my * s.my + c1, D = s.vx + s.vy + c2;
       const float ss = (A * B) / (C * D);
@@ -490,7 +457,6 @@ inline int lt_grid(long total) {
   const long b = (total + LNT - 1) / LNT;
   return (int)(b < 1 ? 1 : b > LMAXB ? LMAXB : b);
 }
-inline int lt_tiles(int n, int t) { return (n + t - 1) / t; }
 
 // LDS bytes a scatter workgroup may take (the default dynamic limit)
 constexpr long SCATTER_LDS = 65536;
@@ -500,7 +466,7 @@ constexpr long SCATTER_LDS = 65536;
 extern "C" {
 
 long um_lossterm_ws(int N, int H, int W) {
-  long tiles = (long)N * lt_tiles(H, LTY) * lt_tiles(W, LTX);
+  long tiles = (long)N * ceil_div(H, LTY) * ceil_div(W, LTX);
   return 8 * (tiles > LMAXB ? tiles : LMAXB);
 }
 
@@ -512,7 +478,7 @@ int um_image_error_k(const float* img, const float* rec, int N, int H, int W, fl
   UM_CHECK_ARG(N >= 1 && H >= 3 && W >= 3, "um_image_error_k: %dx%dx%d (H, W >= 3)", N, H, W);
   UM_CHECK_ARG((ws != nullptr) == (mean_out != nullptr),
                "um_image_error_k: ws and mean_out go together");
-  const int tx = lt_tiles(W, LTX), ty = lt_tiles(H, LTY);
+  const int tx = ceil_div(W, LTX), ty = ceil_div(H, LTY);
   hipLaunchKernelGGL(lt_image_error_kernel, dim3(N * tx * ty), dim3(LNT), 0, st, img, rec, N, H,
                      W, alpha, c1, c2, out, ws, tx, ty);
   UM_LAUNCH_CHECK();
@@ -530,7 +496,7 @@ int um_image_error_bwd(const float* img, const float* rec, int N, int H, int W, 
   UM_CHECK_ARG(N >= 1 && H >= 3 && W >= 3, "um_image_error_bwd: %dx%dx%d (H, W >= 3)", N, H, W);
   UM_CHECK_ARG(wrt == 0 || wrt == 1, "um_image_error_bwd: wrt %d (0 recon, 1 images)", wrt);
   UM_CHECK_ARG(g != nullptr || g_mean != nullptr, "um_image_error_bwd: no upstream gradient");
-  const int tx = lt_tiles(W, LTX), ty = lt_tiles(H, LTY);
+  const int tx = ceil_div(W, LTX), ty = ceil_div(H, LTY);
   hipLaunchKernelGGL(lt_image_error_bwd_kernel, dim3(N * tx * ty, 6), dim3(LNT), 0, st,
                      wrt == 0 ? rec : img, wrt == 0 ? img : rec, N, H, W, alpha, c1, c2, g, g_mean,
                      (float)(1.0 / ((double)N * H * W)), grad, tx, ty);

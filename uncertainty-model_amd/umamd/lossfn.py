@@ -15,7 +15,9 @@
                             loss.py:405-434): the error term on 3x3 average
                             pools, um_loss_pool_fwd / um_loss_pool_bwd
   * ``image_error``         WeightedSSIMLoss.image_error (loss.py:96-131) of an
-                            explicit recon (evaluation)
+                            explicit recon, no autograd, default k1, k2
+                            (evaluation; lossterms.image_error is the
+                            differentiable form, a kernel of its own)
 
 Images are NCHW f32; predictions are the model's disparity tensors (logical
 [N,4,h,w], stored channels-last).  The fused loss re-derives the recon from
