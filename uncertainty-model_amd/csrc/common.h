@@ -291,12 +291,17 @@ __device__ __forceinline__ void stat_slots_finish_t(const double* __restrict__ s
     for (int k = 0; k < PER; ++k)
       v[k] = in ? *reinterpret_cast<const double2*>(slots + ((long)(part + k * SPL) * C + c) * 2)
                 : make_double2(0.0, 0.0);
-    double s0 = 0.0, s1 = 0.0;
+    // pairwise, slot s with slot s + 8, then + 4, ...: the upper levels of the
+    // shuffle tree below, so the 16 slots are summed in the same order for
+    // every SPL and a channel's sums do not depend on the slice width
 #pragma unroll
-    for (int k = 0; k < PER; ++k) {
-      s0 += v[k].x;
-      s1 += v[k].y;
-    }
+    for (int h = PER >> 1; h > 0; h >>= 1)
+#pragma unroll
+      for (int k = 0; k < h; ++k) {
+        v[k].x += v[k + h].x;
+        v[k].y += v[k + h].y;
+      }
+    double s0 = v[0].x, s1 = v[0].y;
 #pragma unroll
     for (int o = SPL >> 1; o > 0; o >>= 1) {
       s0 += __shfl_xor(s0, o, 64);
