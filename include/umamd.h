@@ -820,6 +820,65 @@ int um_value_range(const float* value, const unsigned char* valid, long count, f
 int um_depth_render(const float* value, const unsigned char* valid, const unsigned char* frame,
                     long count, const unsigned char* lut, const float* rparams,
                     const float* range, int inverse, unsigned char* rgb, hipStream_t stream);
+/* 3-D points (umamd/points.py, DepthPipeline(points=...)): the depth map
+ * back-projected through pinhole intrinsics.  intr: DEVICE f32[4] = (fx, fy,
+ * cx, cy) in source pixels, read by the kernels, so a captured graph sees new
+ * values at its next replay.  For pixel (image n, row v, column u), every step
+ * a separate f32 operation, IEEE division:
+ *   Z = depth[n][v][u]
+ *   X = (((float)u - cx) * Z) / fx
+ *   Y = (((float)v - cy) * Z) / fy
+ * u and v are the integer indices: the pixel centre sits AT the integer
+ * coordinate, no half-pixel shift (a caller whose calibration puts the centre
+ * of pixel 0 at 0.5 passes cx - 0.5 and cy - 0.5).  A pixel is kept when
+ * valid[n][v][u] != 0 (any non-zero byte); valid NULL: every pixel is kept.
+ *
+ * um_depth_backproject: depth f32 [N][Hs][Ws], valid u8 [N][Hs][Ws] or NULL
+ * -> the organised map xyz f32 [N][Hs][Ws][3]: (X, Y, Z) at a kept pixel,
+ * (0, 0, 0) elsewhere whatever depth holds there (NaN, inf).  One launch, one
+ * thread per 4 pixels (a 16-byte depth load, a dword of valid, three 16-byte
+ * stores; a scalar form for the tail and for bases that are not aligned:
+ * depth / xyz 16, valid 4).
+ *
+ * um_depth_cloud: the packed cloud over the lattice v % stride == 0 &&
+ * u % stride == 0, Hl = ceil(Hs / stride) x Wl = ceil(Ws / stride) sites per
+ * image.  The kept sites in order, image-major then row-major, are the rows of
+ *   xyzu   f32 [N * Hl * Wl][4]: (X, Y, Z, uncertainty at the site; 0 with
+ *          uncertainty NULL), one 16-byte store per row (16-byte aligned)
+ *   rgba   u8 [N * Hl * Wl][4]: the frame's (r, g, b) at the site and 255, one
+ *          4-byte store per row (4-byte aligned); skipped if frame (u8
+ *          [N][Hs][Ws][3]) or rgba is NULL
+ *   offsets  int [N + 1]: image n owns rows offsets[n] .. offsets[n + 1];
+ *          offsets[0] = 0, offsets[N] the number of points
+ * Rows at and past offsets[N] are not written: their content is unspecified
+ * for the caller (whatever the buffer held).  uncertainty f32 [N][Hs][Ws] or
+ * NULL.  Three launches, no atomics and no state between calls, so the order
+ * is fixed, the result deterministic and the call safe to capture and replay:
+ * (1) the kept sites of every tile -- 1024 consecutive lattice sites of one
+ * image; a tile never spans two images -- into ws; (2) one workgroup of 256
+ * threads turns the counts into their exclusive prefix sums, 256 tiles per
+ * turn of a loop, and writes offsets; (3) every workgroup packs its tile from
+ * that base: 4 sites per thread, thread counts scanned over the 64 lanes
+ * (__shfl_up), wave totals through LDS, so a tile's rows are one contiguous
+ * run.  stride 1 reads 4 consecutive pixels per thread with vector loads where
+ * the addresses allow, stride > 1 gathers.  ws: um_depth_cloud_ws(N, Hs, Ws,
+ * stride) bytes (host query: 4 per tile, N * ceil(Hl * Wl / 1024) tiles; 0 for
+ * sizes the call refuses), 4-byte aligned.
+ * Measured inside DepthPipeline's graph (tools/bench_depth_points.py, MI355X,
+ * 1024x1280, B=1, 39 % of the pixels kept, medians of 3 alternated repeats):
+ * um_depth_backproject adds 0.0143 ms to the 1.1858 ms frame, um_depth_cloud
+ * 0.0186 ms (0.0165 ms at stride 2), both 0.0261 ms; the same cloud from torch
+ * device ops (nonzero, gathers) adds 0.2049 ms and synchronises with the host.
+ * UM_ERR_ARG before any launch: a size or stride < 1; N * Hl * Wl or N * Hs
+ * above INT_MAX; a null depth / intr / xyz, or ws / xyzu / offsets; a float
+ * pointer that is not 4-byte aligned. */
+int um_depth_backproject(const float* depth, const unsigned char* valid, int N, int Hs, int Ws,
+                         const float* intr, float* xyz, hipStream_t stream);
+long um_depth_cloud_ws(int N, int Hs, int Ws, int stride);
+int um_depth_cloud(const float* depth, const unsigned char* valid, const float* uncertainty,
+                   const unsigned char* frame, int N, int Hs, int Ws, int stride,
+                   const float* intr, void* ws, float* xyzu, unsigned char* rgba, int* offsets,
+                   hipStream_t stream);
 
 /* ------------------------------------------------ SyncBN exchange (IPC) ---
  * SyncBatchNorm statistics exchanged device-side over IPC-mapped per-rank

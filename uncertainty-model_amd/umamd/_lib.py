@@ -196,6 +196,9 @@ _SIG = {
     'um_value_range_ws': (_L, [_L]),
     'um_value_range': (_I, [_P, _P, _L, _P, _P, 's']),
     'um_depth_render': (_I, [_P, _P, _P, _L, _P, _P, _P, _I, _P, 's']),
+    'um_depth_backproject': (_I, [_P, _P, _I, _I, _I, _P, _P, 's']),
+    'um_depth_cloud_ws': (_L, [_I, _I, _I, _I]),
+    'um_depth_cloud': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, 's']),
     'um_adam_chunk': (_I, []),
     'um_adam_step_dev': (_I, [_P, _P, _I, _F, _P, _F, _F, _F, _F, _P, 's']),
 }

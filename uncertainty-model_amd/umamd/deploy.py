@@ -16,12 +16,17 @@ adds both ends of the deployment path,
   -> um_depth_render  only with ``render=``: one of the maps coloured and
                   blended over the frame, uint8 [B,Hs,Ws,3] (umamd/render.py;
                   after um_value_range with ``render_range='auto'``)
+  -> um_depth_backproject / um_depth_cloud  only with ``points=``: the depth
+                  back-projected through the camera intrinsics into an
+                  organised [B,Hs,Ws,3] map and / or a packed, coloured cloud
+                  (umamd/points.py; after um_depth_post, independent of the
+                  display stage)
 
 captured as ONE torch.cuda.CUDAGraph over static buffers.  ``__call__``
 copies the frames in and replays; it never synchronises with the host.  The
 calibration and the three thresholds live in a 4-float device block the kernel
 reads, so ``set_params`` needs no recapture; the display stage has a block of
-its own (range and opacities).
+its own (range and opacities) and so has the point stage (the intrinsics).
 """
 from __future__ import annotations
 
@@ -30,6 +35,7 @@ import math
 import torch
 
 from . import _lib as L
+from . import points as P
 from . import render as R
 from ._lib import call, ptr, query
 from .imageprep import resize_coeffs
@@ -37,6 +43,7 @@ from .infer import InferenceEngine, _eval_mode
 
 PARAMS = ('focal_baseline', 'min_disparity', 'max_uncertainty', 'max_lr_error')
 RENDERS = ('disparity', 'depth', 'uncertainty', 'lr_error')
+POINTS = ('map', 'cloud', 'both')
 
 
 def _check_render(render, colour_map, render_range, opacity, invalid_opacity):
@@ -60,6 +67,23 @@ def _check_render(render, colour_map, render_range, opacity, invalid_opacity):
             raise ValueError("DepthPipeline: render_range=(None, None): (lo, hi) or 'auto'")
     return table, rng, R.check_number('DepthPipeline: opacity', opacity), \
         R.check_number('DepthPipeline: invalid_opacity', invalid_opacity)
+
+
+def _check_points(points, intrinsics, point_stride):
+    """the point stage's arguments -> ((fx, fy, cx, cy), stride); raises before
+    any GPU work"""
+    who = 'DepthPipeline'
+    if not isinstance(points, str) or points not in POINTS:
+        raise ValueError(f'{who}: points={points!r}: None or one of {POINTS}')
+    if intrinsics is None:
+        raise ValueError(f'{who}: points={points!r} needs intrinsics=(fx, fy, cx, cy) in source '
+                         f'pixels')
+    intr = P.check_intrinsics(intrinsics, who)
+    stride = P.check_stride(point_stride, who, 'point_stride')
+    if stride != 1 and points == 'map':
+        raise ValueError(f"{who}: point_stride={stride} with points='map': the organised map "
+                         f"has every pixel (the stride thins the cloud)")
+    return intr, stride
 
 
 def _check_frames(frames, shape):
@@ -106,16 +130,33 @@ class DepthPipeline:
     camera image shows through).  ``set_params`` then also takes
     ``render_lo``, ``render_hi`` (not with ``'auto'``), ``opacity`` and
     ``invalid_opacity``.  With ``render=None`` (the default) nothing of this
-    is allocated, launched or returned."""
+    is allocated, launched or returned.
+
+    ``points='map' | 'cloud' | 'both'`` with ``intrinsics=(fx, fy, cx, cy)``
+    (source pixels; the pixel centre at the integer coordinate) adds the point
+    stage to the same graph (umamd/points.py has the definition).  ``'map'``:
+    ``out['xyz']``, f32 [B,Hs,Ws,3], (X, Y, Z) where ``valid`` and 0 elsewhere.
+    ``'cloud'``: the valid pixels of every ``point_stride``-th row and column,
+    packed image by image in row-major order: ``out['cloud_xyzu']`` f32
+    [capacity, 4] (X, Y, Z, uncertainty), ``out['cloud_rgba']`` uint8
+    [capacity, 4] (the frame's colour, 255) and ``out['cloud_offsets']`` int32
+    [B + 1] -- image n owns rows ``offsets[n]:offsets[n + 1]``, the rows from
+    ``offsets[B]`` on are unspecified.  ``cloud()`` reads the offsets (the
+    stage's only synchronisation) and returns one ``(xyzu, rgba)`` pair of
+    views per image.  ``set_params`` then also takes ``fx``, ``fy``, ``cx``,
+    ``cy``.  With ``points=None`` (the default) nothing of this is allocated,
+    launched or returned."""
 
     def __init__(self, model, src_height: int, src_width: int, batch: int = 1, height: int = 256,
                  width: int = 512, scale: float = 1.0, focal_baseline: float = 1.0,
                  min_disparity: float = 1e-3, max_uncertainty: float = math.inf,
                  max_lr_error: float = math.inf, fused: bool = True, capture: bool = True,
                  render=None, colour_map='inferno', render_range='auto', opacity: float = 1.0,
-                 invalid_opacity: float = 0.0, inverse: bool = False):
+                 invalid_opacity: float = 0.0, inverse: bool = False, points=None,
+                 intrinsics=None, point_stride: int = 1):
         rcfg = None if render is None else _check_render(render, colour_map, render_range,
                                                          opacity, invalid_opacity)
+        pcfg = None if points is None else _check_points(points, intrinsics, point_stride)
         B, H, W, Hs, Ws = int(batch), int(height), int(width), int(src_height), int(src_width)
         if H <= 0 or W <= 0 or H % 32 or W % 32:
             raise ValueError(f'image size {H}x{W}: height and width must be multiples of 32')
@@ -169,6 +210,21 @@ class DepthPipeline:
                 self._range = torch.zeros(2, **f32)
                 self._range_ws = torch.zeros(query('um_value_range_ws', B * Hs * Ws),
                                              dtype=torch.uint8, device=dev)
+        self.points = points
+        if pcfg is not None:
+            intr, self.point_stride = pcfg
+            self.intrinsics = dict(zip(P.INTR_PARAMS, intr))
+            self._intr = torch.tensor(intr, **f32)
+            if points in ('map', 'both'):
+                self._xyz = torch.zeros((B, Hs, Ws, 3), **f32)
+            if points in ('cloud', 'both'):
+                s = self.point_stride
+                capacity = B * -(-Hs // s) * -(-Ws // s)
+                self._cloud_xyzu = torch.zeros((capacity, 4), **f32)
+                self._cloud_rgba = torch.zeros((capacity, 4), dtype=torch.uint8, device=dev)
+                self._cloud_offsets = torch.zeros(B + 1, dtype=torch.int32, device=dev)
+                self._cloud_ws = torch.zeros(query('um_depth_cloud_ws', B, Hs, Ws, s),
+                                             dtype=torch.uint8, device=dev)
         self._graph = None
         self._out = None
         self._called = False
@@ -197,6 +253,14 @@ class DepthPipeline:
             call('um_depth_render', ptr(value), ptr(self._valid), ptr(self._frames), B * Hs * Ws,
                  ptr(self._lut), ptr(self._rparams), ptr(self._range), int(self.inverse),
                  ptr(self._render))
+        if self.points in ('map', 'both'):
+            call('um_depth_backproject', ptr(self._depth), ptr(self._valid), B, Hs, Ws,
+                 ptr(self._intr), ptr(self._xyz))
+        if self.points in ('cloud', 'both'):
+            call('um_depth_cloud', ptr(self._depth), ptr(self._valid), ptr(self._uncertainty),
+                 ptr(self._frames), B, Hs, Ws, self.point_stride, ptr(self._intr),
+                 ptr(self._cloud_ws), ptr(self._cloud_xyzu), ptr(self._cloud_rgba),
+                 ptr(self._cloud_offsets))
         return out
 
     def _capture(self):
@@ -226,9 +290,10 @@ class DepthPipeline:
     def set_params(self, **kw):
         """any of focal_baseline, min_disparity, max_uncertainty, max_lr_error
         and, with ``render=``, render_lo, render_hi (a fixed range only),
-        opacity, invalid_opacity: written into the device blocks in place,
-        seen by the next call"""
-        known = PARAMS + (R.RENDER_PARAMS if self.render is not None else ())
+        opacity, invalid_opacity and, with ``points=``, fx, fy, cx, cy: written
+        into the device blocks in place, seen by the next call"""
+        known = PARAMS + (R.RENDER_PARAMS if self.render is not None else ()) + \
+            (P.INTR_PARAMS if self.points is not None else ())
         bad = sorted(set(kw) - set(known))
         if bad:
             raise TypeError(f'DepthPipeline.set_params: unknown {bad}; one of {known}')
@@ -240,6 +305,10 @@ class DepthPipeline:
                                  f"render_range='auto' (the range is found per call)")
             rkw = {k: R.check_number(f'DepthPipeline.set_params: {k}', v)
                    for k, v in rkw.items()}
+        ikw = {k: kw.pop(k) for k in P.INTR_PARAMS if k in kw}
+        if ikw:
+            intr = P.check_intrinsics([ikw.get(k, self.intrinsics[k]) for k in P.INTR_PARAMS],
+                                      'DepthPipeline.set_params')
         if kw:
             self.params.update({k: float(v) for k, v in kw.items()})
             self._params.copy_(torch.tensor([self.params[k] for k in PARAMS],
@@ -248,6 +317,9 @@ class DepthPipeline:
             self.render_params.update(rkw)
             self._rparams.copy_(torch.tensor([self.render_params[k] for k in R.RENDER_PARAMS],
                                              dtype=torch.float32))
+        if ikw:
+            self.intrinsics = dict(zip(P.INTR_PARAMS, intr))
+            self._intr.copy_(torch.tensor(intr, dtype=torch.float32))
 
     def __call__(self, frames: torch.Tensor):
         _check_frames(frames, self.src_shape)
@@ -271,4 +343,19 @@ class DepthPipeline:
                'prediction': self._out.permute(0, 3, 1, 2)[:, :4]}
         if self.render is not None:
             out['render'] = self._render
+        if self.points in ('map', 'both'):
+            out['xyz'] = self._xyz
+        if self.points in ('cloud', 'both'):
+            out.update(cloud_xyzu=self._cloud_xyzu, cloud_rgba=self._cloud_rgba,
+                       cloud_offsets=self._cloud_offsets)
         return out
+
+    def cloud(self):
+        """the cloud of the last call, one ``(xyzu, rgba)`` pair of views per
+        image (umamd.points.split: reads the offsets, which synchronises)"""
+        if self.points not in ('cloud', 'both'):
+            raise L.UmamdError(f"DepthPipeline.cloud() on a pipeline built with "
+                               f"points={self.points!r}")
+        if not self._called:
+            raise L.UmamdError('DepthPipeline.cloud() before the first call')
+        return P.split(self._cloud_xyzu, self._cloud_rgba, self._cloud_offsets)
