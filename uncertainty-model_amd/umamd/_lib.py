@@ -199,6 +199,8 @@ _SIG = {
     'um_depth_backproject': (_I, [_P, _P, _I, _I, _I, _P, _P, 's']),
     'um_depth_cloud_ws': (_L, [_I, _I, _I, _I]),
     'um_depth_cloud': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, 's']),
+    'um_frame_rectify': (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, 's']),
+    'um_valid_and': (_I, [_P, _P, _I, _L, 's']),
     'um_adam_chunk': (_I, []),
     'um_adam_step_dev': (_I, [_P, _P, _I, _F, _P, _F, _F, _F, _F, _P, 's']),
 }

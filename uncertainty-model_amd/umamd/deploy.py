@@ -27,6 +27,18 @@ copies the frames in and replays; it never synchronises with the host.  The
 calibration and the three thresholds live in a 4-float device block the kernel
 reads, so ``set_params`` needs no recapture; the display stage has a block of
 its own (range and opacities) and so has the point stage (the intrinsics).
+
+With ``rectify=`` a stage 0 runs in front, in the same graph (umamd/rectify.py):
+
+  um_frame_rectify  the RAW uint8 frame [B,Hs,Ws,3] undistorted and
+                  stereo-rectified into the uint8 [B,Hr,Wr,3] frame that every
+                  stage above reads, plus the mask of the pixels whose source
+                  lies inside the raw frame
+  um_valid_and    straight after um_depth_post: valid &= inside, so the display
+                  and point stages see the combined mask
+
+The calibration block (or the table) is read by the kernel too:
+``set_calibration`` needs no recapture.
 """
 from __future__ import annotations
 
@@ -36,6 +48,7 @@ import torch
 
 from . import _lib as L
 from . import points as P
+from . import rectify as Q
 from . import render as R
 from ._lib import call, ptr, query
 from .imageprep import resize_coeffs
@@ -145,7 +158,21 @@ class DepthPipeline:
     stage's only synchronisation) and returns one ``(xyzu, rgba)`` pair of
     views per image.  ``set_params`` then also takes ``fx``, ``fy``, ``cx``,
     ``cy``.  With ``points=None`` (the default) nothing of this is allocated,
-    launched or returned."""
+    launched or returned.
+
+    ``rectify=`` a ``umamd.rectify.Calibration`` or ``RemapTable`` adds stage 0
+    to the same graph: ``src_height`` and ``src_width`` stay the camera's RAW
+    size, the frames passed to the call are raw, and the rectified size (Hr,
+    Wr) -- the calibration's ``size`` (default: the raw size) or the table's
+    shape -- is the frame size of every later stage and of every output.
+    ``out['frame']`` is the rectified frame, uint8 [B,Hr,Wr,3], ``out['inside']``
+    (bool [Hr,Wr]) marks the pixels whose source lies inside the raw frame, and
+    ``valid`` is restricted to them.  ``focal_baseline`` and ``intrinsics`` are
+    those of the RECTIFIED camera: ``Calibration.focal_baseline`` and
+    ``.intrinsics``.  ``set_calibration(how)`` replaces the block or the table
+    in place (same mode and sizes), seen by the next call without recapture.
+    With ``rectify=None`` (the default) nothing of this is allocated, launched
+    or returned."""
 
     def __init__(self, model, src_height: int, src_width: int, batch: int = 1, height: int = 256,
                  width: int = 512, scale: float = 1.0, focal_baseline: float = 1.0,
@@ -153,11 +180,19 @@ class DepthPipeline:
                  max_lr_error: float = math.inf, fused: bool = True, capture: bool = True,
                  render=None, colour_map='inferno', render_range='auto', opacity: float = 1.0,
                  invalid_opacity: float = 0.0, inverse: bool = False, points=None,
-                 intrinsics=None, point_stride: int = 1):
+                 intrinsics=None, point_stride: int = 1, rectify=None):
         rcfg = None if render is None else _check_render(render, colour_map, render_range,
                                                          opacity, invalid_opacity)
         pcfg = None if points is None else _check_points(points, intrinsics, point_stride)
         B, H, W, Hs, Ws = int(batch), int(height), int(width), int(src_height), int(src_width)
+        raw = None
+        if rectify is not None:
+            # stage 0: (Hs, Ws) is the rectified size from here on, raw the camera's
+            Q.check_how(rectify, 'DepthPipeline: rectify')
+            raw = (Hs, Ws)
+            Hs, Ws = rectify.out_size(raw)
+            if B >= 1:
+                Q.check_sizes('DepthPipeline: rectify', B, raw[0], raw[1], Hs, Ws)
         if H <= 0 or W <= 0 or H % 32 or W % 32:
             raise ValueError(f'image size {H}x{W}: height and width must be multiples of 32')
         if Hs < 2 or Ws < 2:
@@ -176,11 +211,17 @@ class DepthPipeline:
         self.infer = InferenceEngine(model, B, H, W, scale, fused=fused, capture=False)
         self.model = self.infer.model
         self.shape = (B, 3, H, W)
-        self.src_shape = (B, Hs, Ws, 3)
+        self.src_shape = (B, Hs, Ws, 3) if raw is None else (B, raw[0], raw[1], 3)
+        self.frame_shape = (B, Hs, Ws, 3)  # what the stages after stage 0 read
         self.scale = float(scale)
         self.capture = bool(capture)
         dev = self.infer._in.device
-        self._frames = torch.zeros(self.src_shape, dtype=torch.uint8, device=dev)
+        self._frames = torch.zeros(self.frame_shape, dtype=torch.uint8, device=dev)
+        self.rectify = rectify
+        if rectify is not None:
+            self._raw = torch.zeros(self.src_shape, dtype=torch.uint8, device=dev)
+            self._inside = torch.zeros((Hs, Ws), dtype=torch.uint8, device=dev)
+            self._rect = rectify.data(dev)  # the f32[24] block or the Q5 table
         self._tables = tuple(torch.from_numpy(a).to(dev) for a in (bh, kh, bv, kv))
         self._ks = (ksh, ksv)
         f32 = dict(dtype=torch.float32, device=dev)
@@ -235,8 +276,13 @@ class DepthPipeline:
     # ---------------------------------------------------------------- runs --
     def _run(self):
         B, _, H, W = self.shape
-        _, Hs, Ws, _ = self.src_shape
+        _, Hs, Ws, _ = self.frame_shape
         bh, kh, bv, kv = self._tables
+        if self.rectify is not None:
+            cal, table = (self._rect, None) if self.rectify.mode == 'analytic' else \
+                (None, self._rect)
+            call('um_frame_rectify', ptr(self._raw), B, self.src_shape[1], self.src_shape[2], Hs,
+                 Ws, ptr(cal), ptr(table), ptr(self._frames), ptr(self._inside))
         call('um_frame_prep', B, Hs, Ws, ptr(self._frames), H, W, ptr(bh), ptr(kh), self._ks[0],
              ptr(bv), ptr(kv), self._ks[1], ptr(self.infer._in))
         out = self.infer._forward()
@@ -246,6 +292,8 @@ class DepthPipeline:
         call('um_depth_post', ptr(out), out.stride(0), out.stride(2), B, H, W, Hs, Ws,
              ptr(self._params), ptr(self._disparity), ptr(self._depth), ptr(self._uncertainty),
              ptr(self._lr_error), ptr(self._valid))
+        if self.rectify is not None:
+            call('um_valid_and', ptr(self._valid), ptr(self._inside), B, Hs * Ws)
         if self.render is not None:
             value = getattr(self, '_' + self.render)
             if self.render_auto:
@@ -321,9 +369,27 @@ class DepthPipeline:
             self.intrinsics = dict(zip(P.INTR_PARAMS, intr))
             self._intr.copy_(torch.tensor(intr, dtype=torch.float32))
 
+    def set_calibration(self, how):
+        """Another Calibration (or RemapTable) of the same mode and sizes:
+        written into the device block (table) in place, seen by the next call
+        without recapture.  Another mode or size is a ValueError."""
+        who = 'DepthPipeline.set_calibration'
+        if self.rectify is None:
+            raise ValueError(f'{who} on a pipeline built with rectify=None')
+        Q.check_how(how, who)
+        if how.mode != self.rectify.mode:
+            raise ValueError(f'{who}: a {type(how).__name__} on a pipeline built with a '
+                             f'{type(self.rectify).__name__}: build another pipeline')
+        size = tuple(how.out_size(self.src_shape[1:3]))
+        if size != tuple(self.frame_shape[1:3]):
+            raise ValueError(f'{who}: rectified size {size}, the pipeline was built for '
+                             f'{tuple(self.frame_shape[1:3])}: build another pipeline')
+        self._rect.copy_(how.data(None))
+        self.rectify = how
+
     def __call__(self, frames: torch.Tensor):
         _check_frames(frames, self.src_shape)
-        self._frames.copy_(frames, non_blocking=True)
+        (self._frames if self.rectify is None else self._raw).copy_(frames, non_blocking=True)
         if self._graph is not None:
             self._graph.replay()
         else:
@@ -341,6 +407,9 @@ class DepthPipeline:
                'uncertainty': self._uncertainty, 'lr_error': self._lr_error,
                'valid': self._valid.view(torch.bool),
                'prediction': self._out.permute(0, 3, 1, 2)[:, :4]}
+        if self.rectify is not None:
+            out['frame'] = self._frames
+            out['inside'] = self._inside.view(torch.bool)
         if self.render is not None:
             out['render'] = self._render
         if self.points in ('map', 'both'):
