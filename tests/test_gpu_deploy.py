@@ -1,7 +1,8 @@
 """The deployment path on the GPU (csrc/deploy.hip, umamd/deploy.py):
 um_frame_prep bit for bit against PIL's resize and against um_stereo_prep,
 um_depth_post against the f64 reference of tests/_deploy_ref.py, and
-DepthPipeline end to end (capture, replay, set_params, refresh).
+DepthPipeline end to end (capture, replay, set_params, refresh) and the entries
+each of its configurations launches, in order.
 
 Bars of the float fields: per field max|gpu - ref64| <= 4 x max(max|ref32 -
 ref64|, 2^-23 max|ref64|), ref32 the same reference evaluated in f32 on the
@@ -332,3 +333,49 @@ def test_pipeline_bf16():
     out = _clone(pipe(frames))
     assert 0.2 < float(out['valid'].float().mean()) < 0.8
     _check_against_own_prediction(pipe, out, 'pipeline bf16')
+
+
+# which entries a configuration launches, and in which order
+ENTRIES = ('um_frame_rectify', 'um_frame_prep', 'um_depth_post', 'um_valid_and', 'um_value_range',
+           'um_depth_render', 'um_depth_backproject', 'um_depth_cloud')
+K = (900.0, 900.0, 131.0, 75.0)
+LAUNCHES = {
+    'plain': ({}, 'frame_prep depth_post'),
+    'render_fixed': (dict(render='depth', render_range=(0.0, 40.0)),
+                     'frame_prep depth_post depth_render'),
+    'render_auto': (dict(render='depth', render_range='auto'),
+                    'frame_prep depth_post value_range depth_render'),
+    'points_map': (dict(points='map', intrinsics=K), 'frame_prep depth_post depth_backproject'),
+    'points_cloud': (dict(points='cloud', intrinsics=K), 'frame_prep depth_post depth_cloud'),
+    'points_both': (dict(points='both', intrinsics=K),
+                    'frame_prep depth_post depth_backproject depth_cloud'),
+    'rectify': (dict(rectify=True), 'frame_rectify frame_prep depth_post valid_and'),
+    'all': (dict(rectify=True, render='depth', render_range='auto', points='both'),
+            'frame_rectify frame_prep depth_post valid_and value_range depth_render '
+            'depth_backproject depth_cloud'),
+}
+
+
+@pytest.mark.parametrize('case', sorted(LAUNCHES))
+def test_pipeline_launch_sequence(model, case):
+    """one eager call launches exactly the deployment entries of its
+    configuration, in the fixed order rectify -> prep -> (forward) -> post ->
+    mask-and -> render -> points, and nothing of a stage that is off"""
+    from umamd import _lib as L
+    kw, want = LAUNCHES[case]
+    if kw.get('rectify'):
+        import test_gpu_rectify as TR
+        cam = TR._cam()
+        kw = {**kw, 'rectify': cam, 'focal_baseline': cam.focal_baseline}
+        if 'points' in kw:
+            kw['intrinsics'] = cam.intrinsics
+        pipe = TR._pipe(model, capture=False, **kw)
+        frames = TR.R.frames(TR.B, *TR.RAW, seed=21)
+    else:
+        pipe = _pipe(model, capture=False, **kw)
+        frames = _frames(B, HS, WS, seed=11)
+    assert pipe._graph is None
+    with L.Recorder(ENTRIES) as rec:
+        pipe(frames)
+    torch.cuda.synchronize()
+    assert [item[0] for item in rec.items] == ['um_' + name for name in want.split()]

@@ -434,6 +434,7 @@ def plain(model, frames):
             pipe.set_params(**{k: 500.0})
     for attr in ('_intr', '_xyz', '_cloud_xyzu', '_cloud_rgba', '_cloud_offsets', '_cloud_ws'):
         assert not hasattr(pipe, attr), attr
+    assert pipe._point_stage is None  # where the stage's buffers live
     from umamd._lib import UmamdError
     with pytest.raises(UmamdError, match='points=None'):
         pipe.cloud()
@@ -530,13 +531,14 @@ def test_pipeline_cloud_beside_render(model, frames, plain):
     pipe = TD._pipe(model, points='cloud', **K, **rkw, **gates)
     out = TD._clone(pipe(frames))
     assert sorted(out) == sorted(PLAIN_KEYS + CLOUD_KEYS + ['render'])
-    assert not hasattr(pipe, '_xyz')
+    assert not hasattr(pipe._point_stage, '_xyz')
     assert torch.equal(out['render'], pic)
     for k in base:
         assert torch.equal(out[k], base[k]), k
     _check_pipeline_points(out, frames, K['intrinsics'], map_too=False)
     only_map = TD._pipe(model, points='map', **K, **gates)
     om = only_map(frames)
-    assert sorted(om) == sorted(PLAIN_KEYS + ['xyz']) and not hasattr(only_map, '_cloud_xyzu')
+    assert sorted(om) == sorted(PLAIN_KEYS + ['xyz']) and \
+        not hasattr(only_map._point_stage, '_cloud')
     assert torch.equal(om['xyz'].cpu(), R.backproject_ref(om['depth'], K['intrinsics'],
                                                           om['valid']))

@@ -383,6 +383,7 @@ def test_rectify_none_is_todays_pipeline(model):
     assert sorted(pipe.last()) == PLAIN_KEYS
     for attr in ('_raw', '_inside', '_rect'):
         assert not hasattr(pipe, attr), attr
+    assert pipe._rect_stage is None  # where the stage's buffers live
     assert pipe.rectify is None and pipe.frame_shape == pipe.src_shape
     with pytest.raises(ValueError, match='rectify=None'):
         pipe.set_calibration(_cam())

@@ -262,6 +262,7 @@ def plain(model, frames):
         with pytest.raises(TypeError, match='unknown'):
             pipe.set_params(**{k: 0.5})
     assert not hasattr(pipe, '_render') and not hasattr(pipe, '_rparams')
+    assert pipe._render_stage is None  # where the stage's buffers live
     return gates, out
 
 
@@ -326,7 +327,7 @@ def test_pipeline_render_auto_range(model, frames, plain):
     for fr in (frames, TD._frames(TD.B, TD.HS, TD.WS, seed=12)):  # the range is per call
         out = TD._clone(pipe(fr))
         lo, hi = R.value_range_ref(out['lr_error'], out['valid'])
-        assert torch.equal(pipe._range.cpu(), torch.stack([lo, hi])) and lo < hi
+        assert torch.equal(pipe._render_stage._range.cpu(), torch.stack([lo, hi])) and lo < hi
         want = _ref_of(out, fr, 'lr_error', lo, hi, 1.0, 0.25, True, _lut('viridis'))
         assert torch.equal(out['render'].cpu(), want)
         alone = colourise(out['lr_error'], valid=out['valid'], frame=fr.to(DEV),

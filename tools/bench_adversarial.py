@@ -22,14 +22,11 @@ each repeat), the relative spread between repeats, and captured / eager.
 import argparse
 import json
 import os
-import sys
 import time
 from copy import deepcopy
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (os.path.join(REPO, 'uncertainty-model_amd'), REPO):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import _bench
+from _bench import REPO
 
 
 def main():
@@ -46,18 +43,13 @@ def main():
         ap.error('--steps must be at least 20')
 
     import torch
-    import yaml
 
     import model as M
-    from oracle import model as OM, step as OS
     from train.loss import TukraUncertaintyLoss
     from train.train import _GraphSteps, train_step
     from umamd.optim import Adam
 
-    assert torch.cuda.is_available(), 'needs a GPU'
-    with open(os.path.join(REPO, 'config.yml')) as f:
-        cfg = yaml.safe_load(f)
-    cfg['model']['encoder']['load_graph'] = os.path.join(REPO, cfg['model']['encoder']['load_graph'])
+    m, cfg, g = _bench.build_model(args.dtype)  # training mode, untouched statistics
     cfg['loss']['error_loss_config']['loss_type'] = 'bayesian'
     dcfg = dict(cfg['discriminator'])
     dcfg['load_graph'] = os.path.join(REPO, dcfg['load_graph'])
@@ -66,14 +58,9 @@ def main():
         ch = dcfg['final_conv']['out_channels']
         dcfg['linear_in_features'] = ch * (args.height >> stages) * (args.width >> stages)
     B = args.batch
-    g = torch.Generator().manual_seed(7)
     left = torch.rand(B, 3, args.height, args.width, generator=g).cuda()
     right = torch.rand(B, 3, args.height, args.width, generator=g).cuda()
 
-    m = M.RandomlyConnectedModel(**cfg['model'], dtype=args.dtype)
-    graphs = OM.load_stage_graphs(cfg['model']['encoder'])
-    m.load_state_dict(OS.formula_state_dict(OS.param_specs(cfg['model'], graphs)))
-    m = m.cuda().train()
     torch.manual_seed(0)
     d = M.RandomDiscriminator(**dcfg, dtype=args.dtype).cuda().train()
     lf = TukraUncertaintyLoss(**cfg['loss'])

@@ -30,64 +30,33 @@ pipeline, whether the pipeline was faster in every repeat, and the max-abs
 difference of the composed leg's outputs from the pipeline's on the timed
 frames.
 """
-import argparse
 import json
 import math
-import os
-import sys
 import time
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (os.path.join(REPO, 'uncertainty-model_amd'), REPO):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import _bench
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
-    ap.add_argument('--calls', type=int, default=20, help='minimum timed calls per leg (>= 20)')
-    ap.add_argument('--seconds', type=float, default=1.0, help='timed span per leg to fill')
-    ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--repeats', type=int, default=2)
-    ap.add_argument('--batch', type=int, default=1)
-    ap.add_argument('--src-height', type=int, default=1024)
-    ap.add_argument('--src-width', type=int, default=1280)
-    ap.add_argument('--height', type=int, default=256)
-    ap.add_argument('--width', type=int, default=512)
-    ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp32'])
+    ap = _bench.parser(__doc__, frames=True)
     args = ap.parse_args()
     if args.calls < 20 or args.repeats < 2:
         ap.error('--calls must be at least 20 and --repeats at least 2')
 
     import torch
     import torch.nn.functional as F
-    import yaml
 
-    import model as M
-    from oracle import model as OM, step as OS
     from umamd.deploy import DepthPipeline
     from umamd.imageprep import stereo_prep
     from umamd.infer import InferenceEngine
 
-    assert torch.cuda.is_available(), 'needs a GPU'
-    with open(os.path.join(REPO, 'config.yml')) as f:
-        cfg = yaml.safe_load(f)
-    cfg['model']['encoder']['load_graph'] = os.path.join(REPO, cfg['model']['encoder']['load_graph'])
-    scale = 0.3
+    scale = _bench.SCALE
     B, H, W, Hs, Ws = args.batch, args.height, args.width, args.src_height, args.src_width
-    m = M.RandomlyConnectedModel(**cfg['model'], dtype=args.dtype)
-    graphs = OM.load_stage_graphs(cfg['model']['encoder'])
-    m.load_state_dict(OS.formula_state_dict(OS.param_specs(cfg['model'], graphs)))
-    m = m.cuda().train()
-    g = torch.Generator().manual_seed(7)
-    with torch.no_grad():  # non-trivial running statistics
-        m(torch.rand(2, 3, H, W, generator=g).cuda(), scale)
-    m.eval()
+    m, _, g = _bench.build_model(args.dtype, H, W)
     frames = torch.randint(0, 256, (B, Hs, Ws, 3), generator=g, dtype=torch.uint8).cuda()
     dev = frames.device
 
-    gates = dict(focal_baseline=100.0, min_disparity=0.05 * Ws, max_uncertainty=0.15,
-                 max_lr_error=0.2 * Ws)
+    gates = _bench.depth_gates(Ws)
     fb, min_disp, max_unc, max_lr = gates.values()
     eng = InferenceEngine(m, B, H, W, scale)
     pipes = {'pipeline': DepthPipeline(m, Hs, Ws, batch=B, height=H, width=W, scale=scale,
@@ -121,31 +90,16 @@ def main():
     legs = {'forward': lambda: eng(resized), 'composed': composed,
             'pipeline': lambda: pipes['pipeline'](frames),
             'pipeline_eager': lambda: pipes['pipeline_eager'](frames)}
-    ms = {k: [] for k in legs}
     sync_ms = {k: [] for k in legs}
-    calls = {}
-    for _ in range(args.repeats):
-        for name, leg in legs.items():
-            for _ in range(args.warmup):
-                leg()
+
+    def sync_latency(name, leg):
+        t0 = time.perf_counter()
+        for _ in range(args.calls):
+            leg()
             torch.cuda.synchronize()
-            if name not in calls:  # size the timed span once per leg
-                t0 = time.perf_counter()
-                for _ in range(5):
-                    leg()
-                torch.cuda.synchronize()
-                per = (time.perf_counter() - t0) / 5
-                calls[name] = max(args.calls, min(5000, math.ceil(args.seconds / per)))
-            t0 = time.perf_counter()
-            for _ in range(calls[name]):
-                leg()
-            torch.cuda.synchronize()
-            ms[name].append((time.perf_counter() - t0) * 1e3 / calls[name])
-            t0 = time.perf_counter()
-            for _ in range(args.calls):
-                leg()
-                torch.cuda.synchronize()
-            sync_ms[name].append((time.perf_counter() - t0) * 1e3 / args.calls)
+        sync_ms[name].append((time.perf_counter() - t0) * 1e3 / args.calls)
+    ms, calls = _bench.time_legs(legs, args.repeats, args.warmup, args.calls, args.seconds,
+                                 after=sync_latency)
 
     ref = composed()
     out = pipes['pipeline'](frames)
@@ -154,11 +108,8 @@ def main():
     assert all(math.isfinite(v) for v in diff.values())
 
     def leg_result(name):
-        v = ms[name]
-        mean = sum(v) / len(v)
-        return {'ms_per_frame': round(mean / B, 4), 'ms_per_call': round(mean, 4),
-                'calls': calls[name], 'repeats_ms_per_call': [round(x, 4) for x in v],
-                'spread_rel': round((max(v) - min(v)) / mean, 5),
+        r = _bench.leg_result(ms[name], calls[name], _bench.mean)
+        return {'ms_per_frame': round(_bench.mean(ms[name]) / B, 4), **r,
                 'sync_ms_per_call': [round(x, 4) for x in sync_ms[name]]}
     res = {'bench': 'depth_pipeline', 'batch': B, 'src_height': Hs, 'src_width': Ws, 'height': H,
            'width': W, 'dtype': args.dtype, 'frames': 'device', 'min_calls': args.calls,

@@ -31,62 +31,28 @@ cloud beat torch_ops in every repeat, the number of bytes in which the
 torch_ops cloud differs from the pipeline's, the kept share, and each stage's
 bytes moved over its added time (GB/s, to be read against the HBM rate).
 """
-import argparse
 import json
-import math
-import os
-import statistics
-import sys
-import time
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (os.path.join(REPO, 'uncertainty-model_amd'), REPO):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import _bench
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
-    ap.add_argument('--calls', type=int, default=20, help='minimum timed calls per leg (>= 20)')
-    ap.add_argument('--seconds', type=float, default=1.0, help='timed span per leg to fill')
-    ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--repeats', type=int, default=3)
-    ap.add_argument('--batch', type=int, default=1)
-    ap.add_argument('--src-height', type=int, default=1024)
-    ap.add_argument('--src-width', type=int, default=1280)
-    ap.add_argument('--height', type=int, default=256)
-    ap.add_argument('--width', type=int, default=512)
-    ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp32'])
+    ap = _bench.parser(__doc__, repeats=3, frames=True)
     args = ap.parse_args()
     if args.calls < 20 or args.repeats < 3:
         ap.error('--calls must be at least 20 and --repeats at least 3')
 
     import torch
-    import yaml
 
-    import model as M
-    from oracle import model as OM, step as OS
     from umamd.deploy import DepthPipeline
 
-    assert torch.cuda.is_available(), 'needs a GPU'
-    with open(os.path.join(REPO, 'config.yml')) as f:
-        cfg = yaml.safe_load(f)
-    cfg['model']['encoder']['load_graph'] = os.path.join(REPO, cfg['model']['encoder']['load_graph'])
-    scale = 0.3
+    scale = _bench.SCALE
     B, H, W, Hs, Ws = args.batch, args.height, args.width, args.src_height, args.src_width
-    m = M.RandomlyConnectedModel(**cfg['model'], dtype=args.dtype)
-    graphs = OM.load_stage_graphs(cfg['model']['encoder'])
-    m.load_state_dict(OS.formula_state_dict(OS.param_specs(cfg['model'], graphs)))
-    m = m.cuda().train()
-    g = torch.Generator().manual_seed(7)
-    with torch.no_grad():  # non-trivial running statistics
-        m(torch.rand(2, 3, H, W, generator=g).cuda(), scale)
-    m.eval()
+    m, _, g = _bench.build_model(args.dtype, H, W)
     frames = torch.randint(0, 256, (B, Hs, Ws, 3), generator=g, dtype=torch.uint8).cuda()
     dev = frames.device
 
-    gates = dict(focal_baseline=100.0, min_disparity=0.05 * Ws, max_uncertainty=0.15,
-                 max_lr_error=0.2 * Ws)
+    gates = _bench.depth_gates(Ws)
     kw = dict(batch=B, height=H, width=W, scale=scale, **gates)
     intr = (0.9 * Ws, 0.9 * Ws, (Ws - 1) / 2, (Hs - 1) / 2)
     pkw = dict(intrinsics=intr, **kw)
@@ -113,25 +79,7 @@ def main():
 
     legs = {k: (lambda p=p: p(frames)) for k, p in pipes.items()}
     legs['torch_ops'] = torch_ops
-    ms = {k: [] for k in legs}
-    calls = {}
-    for _ in range(args.repeats):
-        for name, leg in legs.items():
-            for _ in range(args.warmup):
-                leg()
-            torch.cuda.synchronize()
-            if name not in calls:  # size the timed span once per leg
-                t0 = time.perf_counter()
-                for _ in range(5):
-                    leg()
-                torch.cuda.synchronize()
-                per = (time.perf_counter() - t0) / 5
-                calls[name] = max(args.calls, min(5000, math.ceil(args.seconds / per)))
-            t0 = time.perf_counter()
-            for _ in range(calls[name]):
-                leg()
-            torch.cuda.synchronize()
-            ms[name].append((time.perf_counter() - t0) * 1e3 / calls[name])
+    ms, calls = _bench.time_legs(legs, args.repeats, args.warmup, args.calls, args.seconds)
 
     # the same cloud?  bytes that differ from the pipeline's
     oc = pipes['cloud'](frames)
@@ -149,18 +97,12 @@ def main():
     k2 = int(pipes['cloud_stride2'](frames)['cloud_offsets'][-1])
     assert k == int(valid.sum()) and k2 == int(valid[:, ::2, ::2].sum())
 
-    def leg_result(name):
-        v = ms[name]
-        med = statistics.median(v)
-        return {'ms_per_call': round(med, 4), 'calls': calls[name],
-                'repeats_ms_per_call': [round(x, 4) for x in v],
-                'spread_rel': round((max(v) - min(v)) / med, 5)}
     res = {'bench': 'depth_points', 'batch': B, 'src_height': Hs, 'src_width': Ws, 'height': H,
            'width': W, 'dtype': args.dtype, 'frames': 'device', 'intrinsics': list(intr),
            'min_calls': args.calls, 'seconds': args.seconds, 'warmup': args.warmup,
            'repeats': args.repeats, 'statistic': 'median of the repeats',
            'device': torch.cuda.get_device_name(0)}
-    res.update({name: leg_result(name) for name in legs})
+    res.update({name: _bench.leg_result(ms[name], calls[name]) for name in legs})
     med = {name: res[name]['ms_per_call'] for name in legs}
     # bytes a stage moves: the map reads depth (4) and valid (1) and writes 12
     # per pixel; the cloud reads valid twice (count, pack), depth, uncertainty

@@ -36,18 +36,9 @@ beat torch_ops in every repeat, the number of bytes in which the torch_ops and
 host frames differ from the pipeline's (the roundings differ: reported, not
 gated), the inside share and the stage's bytes moved over its added time.
 """
-import argparse
 import json
-import math
-import os
-import statistics
-import sys
-import time
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (os.path.join(REPO, 'uncertainty-model_amd'), REPO):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import _bench
 
 CAMERA = dict(K=(1035.3, 1034.9, 596.5, 520.4), dist=(-0.0006, 0.0041, 0.0003, -0.0009, -0.002),
               angles=(0.003, -0.012, 0.004), P=(1035.0, 1035.0, 640.0, 512.0))
@@ -84,18 +75,8 @@ def f32_map(block, Hr, Wr):
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
-    ap.add_argument('--calls', type=int, default=20, help='minimum timed calls per leg (>= 20)')
+    ap = _bench.parser(__doc__, repeats=3, frames=True)
     ap.add_argument('--host-calls', type=int, default=5, help='timed calls of the host leg')
-    ap.add_argument('--seconds', type=float, default=1.0, help='timed span per leg to fill')
-    ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--repeats', type=int, default=3)
-    ap.add_argument('--batch', type=int, default=1)
-    ap.add_argument('--src-height', type=int, default=1024)
-    ap.add_argument('--src-width', type=int, default=1280)
-    ap.add_argument('--height', type=int, default=256)
-    ap.add_argument('--width', type=int, default=512)
-    ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp32'])
     ap.add_argument('--out', default=None, help='also write the JSON line to this file')
     args = ap.parse_args()
     if args.calls < 20 or args.repeats < 3 or args.host_calls < 1:
@@ -104,37 +85,21 @@ def main():
     import numpy as np
     import torch
     import torch.nn.functional as F
-    import yaml
     from scipy import ndimage
 
-    import model as M
-    from oracle import model as OM, step as OS
     from umamd.deploy import DepthPipeline
     from umamd.rectify import Calibration, RemapTable
 
-    assert torch.cuda.is_available(), 'needs a GPU'
-    with open(os.path.join(REPO, 'config.yml')) as f:
-        cfg = yaml.safe_load(f)
-    enc = cfg['model']['encoder']
-    enc['load_graph'] = os.path.join(REPO, enc['load_graph'])
-    scale = 0.3
+    scale = _bench.SCALE
     B, H, W, Hs, Ws = args.batch, args.height, args.width, args.src_height, args.src_width
-    m = M.RandomlyConnectedModel(**cfg['model'], dtype=args.dtype)
-    graphs = OM.load_stage_graphs(cfg['model']['encoder'])
-    m.load_state_dict(OS.formula_state_dict(OS.param_specs(cfg['model'], graphs)))
-    m = m.cuda().train()
-    g = torch.Generator().manual_seed(7)
-    with torch.no_grad():  # non-trivial running statistics
-        m(torch.rand(2, 3, H, W, generator=g).cuda(), scale)
-    m.eval()
+    m, _, g = _bench.build_model(args.dtype, H, W)
     host_frames = torch.randint(0, 256, (B, Hs, Ws, 3), generator=g, dtype=torch.uint8)
     frames = host_frames.cuda()
     dev = frames.device
 
     cal = Calibration(CAMERA['K'], CAMERA['dist'], R=rot(*CAMERA['angles']), P=CAMERA['P'])
     mx, my = f32_map(cal.block(), Hs, Ws)
-    gates = dict(focal_baseline=100.0, min_disparity=0.05 * Ws, max_uncertainty=0.15,
-                 max_lr_error=0.2 * Ws)
+    gates = _bench.depth_gates(Ws)
     kw = dict(batch=B, height=H, width=W, scale=scale, **gates)
     plain = DepthPipeline(m, Hs, Ws, **kw)
     analytic = DepthPipeline(m, Hs, Ws, rectify=cal, **kw)
@@ -168,25 +133,8 @@ def main():
             'table': lambda: table(frames),
             'torch_ops': lambda: plain(torch_frame()),
             'host': lambda: plain(host_frame())}
-    ms = {k: [] for k in legs}
-    calls = {'host': args.host_calls}
-    for _ in range(args.repeats):
-        for name, leg in legs.items():
-            for _ in range(1 if name == 'host' else args.warmup):
-                leg()
-            torch.cuda.synchronize()
-            if name not in calls:  # size the timed span once per leg
-                t0 = time.perf_counter()
-                for _ in range(5):
-                    leg()
-                torch.cuda.synchronize()
-                per = (time.perf_counter() - t0) / 5
-                calls[name] = max(args.calls, min(5000, math.ceil(args.seconds / per)))
-            t0 = time.perf_counter()
-            for _ in range(calls[name]):
-                leg()
-            torch.cuda.synchronize()
-            ms[name].append((time.perf_counter() - t0) * 1e3 / calls[name])
+    ms, calls = _bench.time_legs(legs, args.repeats, {'default': args.warmup, 'host': 1},
+                                 args.calls, args.seconds, fixed_calls={'host': args.host_calls})
 
     # the same frame?  bytes that differ from the pipeline's (the roundings differ)
     oa = {k: v.clone() for k, v in analytic(frames).items()}
@@ -201,18 +149,12 @@ def main():
     step_torch = int((torch_frame().int() - oa['frame'].int()).abs().max())
     step_host = int((host_frame().to(dev).int() - oa['frame'].int()).abs().max())
 
-    def leg_result(name):
-        v = ms[name]
-        med = statistics.median(v)
-        return {'ms_per_call': round(med, 4), 'calls': calls[name],
-                'repeats_ms_per_call': [round(x, 4) for x in v],
-                'spread_rel': round((max(v) - min(v)) / med, 5)}
     res = {'bench': 'depth_rectify', 'batch': B, 'src_height': Hs, 'src_width': Ws,
            'rect_height': Hs, 'rect_width': Ws, 'height': H, 'width': W, 'dtype': args.dtype,
            'frames': 'device (host leg: host)', 'camera': CAMERA, 'min_calls': args.calls,
            'seconds': args.seconds, 'warmup': args.warmup, 'repeats': args.repeats,
            'statistic': 'median of the repeats', 'device': torch.cuda.get_device_name(0)}
-    res.update({name: leg_result(name) for name in legs})
+    res.update({name: _bench.leg_result(ms[name], calls[name]) for name in legs})
     med = {name: res[name]['ms_per_call'] for name in legs}
     # bytes the stage moves per output pixel: 3 written + 1 of inside, about 3
     # read (every raw byte once through the caches; the four taps of a pixel

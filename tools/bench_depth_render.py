@@ -34,33 +34,14 @@ torch_ops / fixed and host / fixed, whether fixed beat torch_ops in every
 repeat, and the number of bytes in which legs (d) and (e) differ from the
 pipeline's picture.
 """
-import argparse
 import json
-import math
-import os
-import statistics
-import sys
-import time
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (os.path.join(REPO, 'uncertainty-model_amd'), REPO):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import _bench
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
-    ap.add_argument('--calls', type=int, default=20, help='minimum timed calls per leg (>= 20)')
+    ap = _bench.parser(__doc__, repeats=3, frames=True)
     ap.add_argument('--host-calls', type=int, default=30, help='timed calls of the host leg')
-    ap.add_argument('--seconds', type=float, default=1.0, help='timed span per leg to fill')
-    ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--repeats', type=int, default=3)
-    ap.add_argument('--batch', type=int, default=1)
-    ap.add_argument('--src-height', type=int, default=1024)
-    ap.add_argument('--src-width', type=int, default=1280)
-    ap.add_argument('--height', type=int, default=256)
-    ap.add_argument('--width', type=int, default=512)
-    ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp32'])
     ap.add_argument('--opacity', type=float, default=0.6)
     args = ap.parse_args()
     if args.calls < 20 or args.repeats < 2 or args.host_calls < 1:
@@ -69,33 +50,18 @@ def main():
     import matplotlib.pyplot as plt
     import numpy as np
     import torch
-    import yaml
 
-    import model as M
-    from oracle import model as OM, step as OS
     from umamd.deploy import DepthPipeline
     from umamd.render import lut
 
-    assert torch.cuda.is_available(), 'needs a GPU'
-    with open(os.path.join(REPO, 'config.yml')) as f:
-        cfg = yaml.safe_load(f)
-    cfg['model']['encoder']['load_graph'] = os.path.join(REPO, cfg['model']['encoder']['load_graph'])
-    scale = 0.3
+    scale = _bench.SCALE
     B, H, W, Hs, Ws = args.batch, args.height, args.width, args.src_height, args.src_width
-    m = M.RandomlyConnectedModel(**cfg['model'], dtype=args.dtype)
-    graphs = OM.load_stage_graphs(cfg['model']['encoder'])
-    m.load_state_dict(OS.formula_state_dict(OS.param_specs(cfg['model'], graphs)))
-    m = m.cuda().train()
-    g = torch.Generator().manual_seed(7)
-    with torch.no_grad():  # non-trivial running statistics
-        m(torch.rand(2, 3, H, W, generator=g).cuda(), scale)
-    m.eval()
+    m, _, g = _bench.build_model(args.dtype, H, W)
     frames_host = torch.randint(0, 256, (B, Hs, Ws, 3), generator=g, dtype=torch.uint8)
     frames = frames_host.cuda()
     dev = frames.device
 
-    gates = dict(focal_baseline=100.0, min_disparity=0.05 * Ws, max_uncertainty=0.15,
-                 max_lr_error=0.2 * Ws)
+    gates = _bench.depth_gates(Ws)
     kw = dict(batch=B, height=H, width=W, scale=scale, **gates)
     plain = DepthPipeline(m, Hs, Ws, **kw)
     out = plain(frames)
@@ -135,49 +101,26 @@ def main():
 
     legs = {'plain': lambda: plain(frames), 'fixed': lambda: fixed(frames),
             'auto': lambda: auto(frames), 'torch_ops': torch_ops, 'host': host}
-    ms = {k: [] for k in legs}
-    calls = {'host': args.host_calls}
-    for _ in range(args.repeats):
-        for name, leg in legs.items():
-            for _ in range(2 if name == 'host' else args.warmup):
-                leg()
-            torch.cuda.synchronize()
-            if name not in calls:  # size the timed span once per leg
-                t0 = time.perf_counter()
-                for _ in range(5):
-                    leg()
-                torch.cuda.synchronize()
-                per = (time.perf_counter() - t0) / 5
-                calls[name] = max(args.calls, min(5000, math.ceil(args.seconds / per)))
-            t0 = time.perf_counter()
-            for _ in range(calls[name]):
-                leg()
-            torch.cuda.synchronize()
-            ms[name].append((time.perf_counter() - t0) * 1e3 / calls[name])
+    ms, calls = _bench.time_legs(legs, args.repeats, {'default': args.warmup, 'host': 2},
+                                 args.calls, args.seconds, fixed_calls={'host': args.host_calls})
 
     # the same picture?  bytes that differ from the pipeline's
     pic = fixed(frames)['render'].clone()
     pic_auto = auto(frames)['render'].clone()
-    rng = auto._range.tolist()
+    rng = auto._render_stage._range.tolist()
     diff = {'torch_ops': int((torch_ops() != pic).sum()),
             'host': int((torch.from_numpy(host()).to(dev) != pic).sum())}
     o = plain(frames)
     vd = o['depth'][o['valid']]
     assert rng == [float(vd.min()), float(vd.max())], rng
 
-    def leg_result(name):
-        v = ms[name]
-        med = statistics.median(v)
-        return {'ms_per_call': round(med, 4), 'calls': calls[name],
-                'repeats_ms_per_call': [round(x, 4) for x in v],
-                'spread_rel': round((max(v) - min(v)) / med, 5)}
     res = {'bench': 'depth_render', 'batch': B, 'src_height': Hs, 'src_width': Ws, 'height': H,
            'width': W, 'dtype': args.dtype, 'frames': 'device', 'render': 'depth',
            'colour_map': 'inferno', 'render_range': [lo, hi], 'opacity': op,
            'min_calls': args.calls, 'seconds': args.seconds, 'warmup': args.warmup,
            'repeats': args.repeats, 'statistic': 'median of the repeats',
            'device': torch.cuda.get_device_name(0)}
-    res.update({name: leg_result(name) for name in legs})
+    res.update({name: _bench.leg_result(ms[name], calls[name]) for name in legs})
     med = {k: res[k]['ms_per_call'] for k in legs}
     res['fixed_minus_plain_ms'] = round(med['fixed'] - med['plain'], 4)
     res['auto_minus_plain_ms'] = round(med['auto'] - med['plain'], 4)

@@ -23,60 +23,33 @@ each repeat, the relative spread), captured / eager, whether the captured leg
 was faster in every alternated repeat, and the absolute differences of the
 four metrics between the legs with the random maps fixed.
 """
-import argparse
 import contextlib
 import io
 import json
 import math
 import os
-import sys
-import time
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (os.path.join(REPO, 'uncertainty-model_amd'), REPO):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import _bench
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
-    ap.add_argument('--calls', type=int, default=3, help='minimum timed evaluations per leg')
-    ap.add_argument('--seconds', type=float, default=2.0, help='timed span per leg to fill')
-    ap.add_argument('--warmup', type=int, default=2)
-    ap.add_argument('--repeats', type=int, default=3)
+    ap = _bench.parser(__doc__, calls=3, seconds=2.0, warmup=2, repeats=3)
     ap.add_argument('--batch', type=int, default=8)
     ap.add_argument('--nbatches', type=int, default=8)
-    ap.add_argument('--height', type=int, default=256)
-    ap.add_argument('--width', type=int, default=512)
-    ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp32'])
     args = ap.parse_args()
     if args.calls < 3 or args.repeats < 2:
         ap.error('--calls must be at least 3 and --repeats at least 2')
 
     import torch
-    import yaml
 
-    import model as M
     import train.sparsification as S
-    from oracle import model as OM, step as OS
     from train.evaluate import evaluate_model, evaluate_model_captured
     from umamd.evalengine import EvaluationEngine
 
-    assert torch.cuda.is_available(), 'needs a GPU'
     os.environ.pop('UMAMD_EVAL_ENGINE', None)  # the eager leg is today's code
-    with open(os.path.join(REPO, 'config.yml')) as f:
-        cfg = yaml.safe_load(f)
-    cfg['model']['encoder']['load_graph'] = os.path.join(REPO, cfg['model']['encoder']['load_graph'])
-    scale = 0.3
+    scale = _bench.SCALE
     B, H, W = args.batch, args.height, args.width
-    m = M.RandomlyConnectedModel(**cfg['model'], dtype=args.dtype)
-    graphs = OM.load_stage_graphs(cfg['model']['encoder'])
-    m.load_state_dict(OS.formula_state_dict(OS.param_specs(cfg['model'], graphs)))
-    m = m.cuda().train()
-    g = torch.Generator().manual_seed(7)
-    with torch.no_grad():  # non-trivial running statistics
-        m(torch.rand(2, 3, H, W, generator=g).cuda(), scale)
-    m.eval()
+    m, _, g = _bench.build_model(args.dtype, H, W)
 
     class Loader(list):
         batch_size = B
@@ -89,24 +62,10 @@ def main():
         with contextlib.redirect_stdout(io.StringIO()):  # the no_pbar summary
             return fn(m, loader, None, scale=scale, no_pbar=True, device='cuda')
     legs = {'eager': lambda: run(evaluate_model), 'captured': lambda: run(evaluate_model_captured)}
-    ms = {k: [] for k in legs}
-    calls = {}
-    for _ in range(args.repeats):
-        for name, leg in legs.items():
-            for _ in range(args.warmup):
-                leg()
-            torch.cuda.synchronize()
-            if name not in calls:  # size the timed span once per leg
-                t0 = time.perf_counter()
-                leg()
-                torch.cuda.synchronize()
-                per = time.perf_counter() - t0
-                calls[name] = max(args.calls, min(200, math.ceil(args.seconds / per)))
-            t0 = time.perf_counter()
-            for _ in range(calls[name]):
-                leg()
-            torch.cuda.synchronize()
-            ms[name].append((time.perf_counter() - t0) * 1e3 / (calls[name] * args.nbatches))
+    # one call is one evaluation of the loader: sized from one, at most 200
+    ms, calls = _bench.time_legs(legs, args.repeats, args.warmup, args.calls, args.seconds,
+                                 probe=1, cap=200)
+    ms = {k: [x / args.nbatches for x in v] for k, v in ms.items()}  # per batch
 
     # the four metrics of both legs on the same fixed random maps
     real_step, real_curve = EvaluationEngine.step, S.random_curve

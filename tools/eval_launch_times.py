@@ -6,13 +6,8 @@ one batch of ``EvaluationEngine(capture=False)`` against one batch of
 line (profiles/eval/launch_times.json)."""
 import collections
 import json
-import os
-import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (os.path.join(REPO, 'uncertainty-model_amd'), REPO):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import _bench
 
 NAMES = ['um_eval_maps', 'um_eval_pool', 'um_eval_accum', 'um_spars_sort', 'um_spars_curve',
          'um_warp', 'um_ssim_gauss', 'um_image_error', 'um_avgpool_valid']
@@ -20,24 +15,14 @@ NAMES = ['um_eval_maps', 'um_eval_pool', 'um_eval_accum', 'um_spars_sort', 'um_s
 
 def main():
     import torch
-    import yaml
 
-    import model as M
-    from oracle import model as OM, step as OS
     from train.evaluate import _eager_batch
     from umamd import _lib as L
     from umamd.evalengine import EvaluationEngine
 
-    assert torch.cuda.is_available(), 'needs a GPU'
-    with open(os.path.join(REPO, 'config.yml')) as f:
-        cfg = yaml.safe_load(f)
-    cfg['model']['encoder']['load_graph'] = os.path.join(REPO, cfg['model']['encoder']['load_graph'])
-    B, H, W, scale, timed = 8, 256, 512, 0.3, 5
-    m = M.RandomlyConnectedModel(**cfg['model'], dtype='bf16')
-    graphs = OM.load_stage_graphs(cfg['model']['encoder'])
-    m.load_state_dict(OS.formula_state_dict(OS.param_specs(cfg['model'], graphs)))
-    m = m.cuda().eval()
-    g = torch.Generator().manual_seed(7)
+    B, H, W, scale, timed = 8, 256, 512, _bench.SCALE, 5
+    m, _, g = _bench.build_model('bf16')  # untouched running statistics
+    m.eval()
     left = torch.rand(B, 3, H, W, generator=g).cuda()
     right = torch.rand(B, 3, H, W, generator=g).cuda()
     eng = EvaluationEngine(m, B, H, W, scale, capture=False)

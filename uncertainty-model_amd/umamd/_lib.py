@@ -337,6 +337,26 @@ def require_device(t: torch.Tensor):
                          'the HIP path has no CPU fallback')
 
 
+def check_tensor(who: str, name: str, t, dtypes, what: str, shape=None):
+    """``t`` is a tensor of one of ``dtypes`` (``what`` names them in the
+    message) and, with ``shape``, contiguous of exactly that shape"""
+    if not torch.is_tensor(t) or t.dtype not in dtypes:
+        raise TypeError(f'{who}: {name}: {what} tensor expected, got '
+                        f'{t.dtype if torch.is_tensor(t) else type(t).__name__}')
+    if shape is not None and (tuple(t.shape) != tuple(shape) or not t.is_contiguous()):
+        raise ValueError(f'{who}: {name}: contiguous {tuple(shape)} expected, got '
+                         f'{tuple(t.shape)} with strides {t.stride()}')
+
+
+def check_same_device(who: str, name: str, first: torch.Tensor, **others):
+    """``first`` (called ``name``) is on a HIP device and every tensor of
+    ``others`` that is not None is on the same one"""
+    require_device(first)
+    for k, t in others.items():
+        if t is not None and t.device != first.device:
+            raise UmamdError(f'{who}: {k} on {t.device}, {name} on {first.device}')
+
+
 def dtype_code(dt: torch.dtype) -> int:
     if dt == torch.float32:
         return UM_F32

@@ -47,56 +47,20 @@ import math
 import torch
 
 from . import _lib as L
-from . import points as P
-from . import rectify as Q
-from . import render as R
 from ._lib import call, ptr, query
 from .imageprep import resize_coeffs
-from .infer import InferenceEngine, _eval_mode
+from .infer import InferenceEngine, _eval_mode, capture_graph, check_prediction, refresh_engine
+from .points import POINTS, PointStage, split  # noqa: F401 (POINTS: a name of this module too)
+from .rectify import RectifyStage
+from .render import RENDERS, RenderStage
 
 PARAMS = ('focal_baseline', 'min_disparity', 'max_uncertainty', 'max_lr_error')
-RENDERS = ('disparity', 'depth', 'uncertainty', 'lr_error')
-POINTS = ('map', 'cloud', 'both')
 
 
-def _check_render(render, colour_map, render_range, opacity, invalid_opacity):
-    """the display stage's arguments -> (table, (lo, hi) or None for 'auto',
-    opacity, invalid_opacity); raises before any GPU work"""
-    if not isinstance(render, str) or render not in RENDERS:
-        raise ValueError(f'DepthPipeline: render={render!r}: None or one of {RENDERS}')
-    table = R.lut(colour_map)
-    if isinstance(render_range, str):
-        if render_range != 'auto':
-            raise ValueError(f"DepthPipeline: render_range={render_range!r}: (lo, hi) or 'auto'")
-        rng = None
-    else:
-        try:
-            lo, hi = render_range
-        except (TypeError, ValueError):
-            raise ValueError(f"DepthPipeline: render_range={render_range!r}: (lo, hi) or "
-                             f"'auto'") from None
-        rng = R.check_range(lo, hi, 'DepthPipeline: render_range')
-        if rng is None:
-            raise ValueError("DepthPipeline: render_range=(None, None): (lo, hi) or 'auto'")
-    return table, rng, R.check_number('DepthPipeline: opacity', opacity), \
-        R.check_number('DepthPipeline: invalid_opacity', invalid_opacity)
-
-
-def _check_points(points, intrinsics, point_stride):
-    """the point stage's arguments -> ((fx, fy, cx, cy), stride); raises before
-    any GPU work"""
-    who = 'DepthPipeline'
-    if not isinstance(points, str) or points not in POINTS:
-        raise ValueError(f'{who}: points={points!r}: None or one of {POINTS}')
-    if intrinsics is None:
-        raise ValueError(f'{who}: points={points!r} needs intrinsics=(fx, fy, cx, cy) in source '
-                         f'pixels')
-    intr = P.check_intrinsics(intrinsics, who)
-    stride = P.check_stride(point_stride, who, 'point_stride')
-    if stride != 1 and points == 'map':
-        raise ValueError(f"{who}: point_stride={stride} with points='map': the organised map "
-                         f"has every pixel (the stride thins the cloud)")
-    return intr, stride
+def _write(block, params, keys, new):
+    """``new`` into the host dict and the whole device block (in place)"""
+    params.update(new)
+    block.copy_(torch.tensor([params[k] for k in keys], dtype=torch.float32))
 
 
 def _check_frames(frames, shape):
@@ -181,18 +145,17 @@ class DepthPipeline:
                  render=None, colour_map='inferno', render_range='auto', opacity: float = 1.0,
                  invalid_opacity: float = 0.0, inverse: bool = False, points=None,
                  intrinsics=None, point_stride: int = 1, rectify=None):
-        rcfg = None if render is None else _check_render(render, colour_map, render_range,
-                                                         opacity, invalid_opacity)
-        pcfg = None if points is None else _check_points(points, intrinsics, point_stride)
+        # every stage checks its own arguments, in this order, before any GPU work
+        self._render_stage = None if render is None else RenderStage(
+            render, colour_map, render_range, opacity, invalid_opacity, inverse)
+        self._point_stage = None if points is None else PointStage(points, intrinsics,
+                                                                   point_stride)
         B, H, W, Hs, Ws = int(batch), int(height), int(width), int(src_height), int(src_width)
-        raw = None
-        if rectify is not None:
-            # stage 0: (Hs, Ws) is the rectified size from here on, raw the camera's
-            Q.check_how(rectify, 'DepthPipeline: rectify')
-            raw = (Hs, Ws)
-            Hs, Ws = rectify.out_size(raw)
-            if B >= 1:
-                Q.check_sizes('DepthPipeline: rectify', B, raw[0], raw[1], Hs, Ws)
+        rect = self._rect_stage = None if rectify is None else RectifyStage(rectify, B, Hs, Ws)
+        self.render, self.points = render, points
+        self.src_shape = (B, Hs, Ws, 3)  # the camera's raw size
+        if rect is not None:
+            Hs, Ws = rect.size  # the rectified size from here on
         if H <= 0 or W <= 0 or H % 32 or W % 32:
             raise ValueError(f'image size {H}x{W}: height and width must be multiples of 32')
         if Hs < 2 or Ws < 2:
@@ -211,61 +174,27 @@ class DepthPipeline:
         self.infer = InferenceEngine(model, B, H, W, scale, fused=fused, capture=False)
         self.model = self.infer.model
         self.shape = (B, 3, H, W)
-        self.src_shape = (B, Hs, Ws, 3) if raw is None else (B, raw[0], raw[1], 3)
         self.frame_shape = (B, Hs, Ws, 3)  # what the stages after stage 0 read
         self.scale = float(scale)
         self.capture = bool(capture)
         dev = self.infer._in.device
-        self._frames = torch.zeros(self.frame_shape, dtype=torch.uint8, device=dev)
-        self.rectify = rectify
-        if rectify is not None:
-            self._raw = torch.zeros(self.src_shape, dtype=torch.uint8, device=dev)
-            self._inside = torch.zeros((Hs, Ws), dtype=torch.uint8, device=dev)
-            self._rect = rectify.data(dev)  # the f32[24] block or the Q5 table
+        self._after = [st for st in (self._render_stage, self._point_stage) if st is not None]
+        self._stages = ([] if rect is None else [rect]) + self._after
+        for st in self._stages:
+            st.allocate(dev, B, Hs, Ws)
+        self._frames = torch.zeros(self.frame_shape, dtype=torch.uint8, device=dev) \
+            if rect is None else rect.frames
+        self._input = self._frames if rect is None else rect.raw_frames  # what a call fills
         self._tables = tuple(torch.from_numpy(a).to(dev) for a in (bh, kh, bv, kv))
         self._ks = (ksh, ksv)
         f32 = dict(dtype=torch.float32, device=dev)
-        self._disparity = torch.zeros((B, Hs, Ws), **f32)
-        self._depth = torch.zeros((B, Hs, Ws), **f32)
-        self._uncertainty = torch.zeros((B, Hs, Ws), **f32)
-        self._lr_error = torch.zeros((B, Hs, Ws), **f32)
-        self._valid = torch.zeros((B, Hs, Ws), dtype=torch.uint8, device=dev)
+        self._maps = {k: torch.zeros((B, Hs, Ws), **f32) for k in RENDERS}
+        self._maps['valid'] = torch.zeros((B, Hs, Ws), dtype=torch.uint8, device=dev)
         self.params = {'focal_baseline': float(focal_baseline),
                        'min_disparity': float(min_disparity),
                        'max_uncertainty': float(max_uncertainty),
                        'max_lr_error': float(max_lr_error)}
         self._params = torch.tensor([self.params[k] for k in PARAMS], **f32)
-        self.render = render
-        if rcfg is not None:
-            table, rng, op, iop = rcfg
-            self.inverse = bool(inverse)
-            self.render_auto = rng is None
-            lo, hi = rng or (0.0, 1.0)  # 'auto': replaced by the device range
-            self.render_params = {'render_lo': lo, 'render_hi': hi, 'opacity': op,
-                                  'invalid_opacity': iop}
-            self._rparams = torch.tensor([self.render_params[k] for k in R.RENDER_PARAMS], **f32)
-            self._lut = table.to(dev)
-            self._render = torch.zeros((B, Hs, Ws, 3), dtype=torch.uint8, device=dev)
-            self._range = self._range_ws = None
-            if self.render_auto:
-                self._range = torch.zeros(2, **f32)
-                self._range_ws = torch.zeros(query('um_value_range_ws', B * Hs * Ws),
-                                             dtype=torch.uint8, device=dev)
-        self.points = points
-        if pcfg is not None:
-            intr, self.point_stride = pcfg
-            self.intrinsics = dict(zip(P.INTR_PARAMS, intr))
-            self._intr = torch.tensor(intr, **f32)
-            if points in ('map', 'both'):
-                self._xyz = torch.zeros((B, Hs, Ws, 3), **f32)
-            if points in ('cloud', 'both'):
-                s = self.point_stride
-                capacity = B * -(-Hs // s) * -(-Ws // s)
-                self._cloud_xyzu = torch.zeros((capacity, 4), **f32)
-                self._cloud_rgba = torch.zeros((capacity, 4), dtype=torch.uint8, device=dev)
-                self._cloud_offsets = torch.zeros(B + 1, dtype=torch.int32, device=dev)
-                self._cloud_ws = torch.zeros(query('um_depth_cloud_ws', B, Hs, Ws, s),
-                                             dtype=torch.uint8, device=dev)
         self._graph = None
         self._out = None
         self._called = False
@@ -273,123 +202,74 @@ class DepthPipeline:
             if self.capture:
                 self._capture()
 
+    # what the stages hold, readable as the pipeline's (AttributeError without the stage)
+    rectify = property(lambda self: self._rect_stage and self._rect_stage.how)
+    render_params = property(lambda self: self._render_stage.params)
+    render_auto = property(lambda self: self._render_stage.auto)
+    inverse = property(lambda self: self._render_stage.inverse)
+    intrinsics = property(lambda self: self._point_stage.params)
+    point_stride = property(lambda self: self._point_stage.stride)
+
     # ---------------------------------------------------------------- runs --
     def _run(self):
+        """rectify -> prep -> forward -> post -> mask-and -> render -> points"""
         B, _, H, W = self.shape
         _, Hs, Ws, _ = self.frame_shape
         bh, kh, bv, kv = self._tables
-        if self.rectify is not None:
-            cal, table = (self._rect, None) if self.rectify.mode == 'analytic' else \
-                (None, self._rect)
-            call('um_frame_rectify', ptr(self._raw), B, self.src_shape[1], self.src_shape[2], Hs,
-                 Ws, ptr(cal), ptr(table), ptr(self._frames), ptr(self._inside))
+        if self._rect_stage is not None:
+            self._rect_stage.before_prep()
         call('um_frame_prep', B, Hs, Ws, ptr(self._frames), H, W, ptr(bh), ptr(kh), self._ks[0],
              ptr(bv), ptr(kv), self._ks[1], ptr(self.infer._in))
         out = self.infer._forward()
-        if out.dtype != torch.float32 or out.stride(3) != 1 or out.stride(1) != W * out.stride(2):
-            raise L.UmamdError(f'DepthPipeline: prediction {out.dtype} with strides '
-                               f'{out.stride()} is not an NHWC f32 image')
+        check_prediction('DepthPipeline', out, W)
         call('um_depth_post', ptr(out), out.stride(0), out.stride(2), B, H, W, Hs, Ws,
-             ptr(self._params), ptr(self._disparity), ptr(self._depth), ptr(self._uncertainty),
-             ptr(self._lr_error), ptr(self._valid))
-        if self.rectify is not None:
-            call('um_valid_and', ptr(self._valid), ptr(self._inside), B, Hs * Ws)
-        if self.render is not None:
-            value = getattr(self, '_' + self.render)
-            if self.render_auto:
-                R.value_range(value, self._valid, out=self._range, ws=self._range_ws)
-            call('um_depth_render', ptr(value), ptr(self._valid), ptr(self._frames), B * Hs * Ws,
-                 ptr(self._lut), ptr(self._rparams), ptr(self._range), int(self.inverse),
-                 ptr(self._render))
-        if self.points in ('map', 'both'):
-            call('um_depth_backproject', ptr(self._depth), ptr(self._valid), B, Hs, Ws,
-                 ptr(self._intr), ptr(self._xyz))
-        if self.points in ('cloud', 'both'):
-            call('um_depth_cloud', ptr(self._depth), ptr(self._valid), ptr(self._uncertainty),
-                 ptr(self._frames), B, Hs, Ws, self.point_stride, ptr(self._intr),
-                 ptr(self._cloud_ws), ptr(self._cloud_xyzu), ptr(self._cloud_rgba),
-                 ptr(self._cloud_offsets))
+             ptr(self._params), *[ptr(self._maps[k]) for k in RENDERS + ('valid',)])
+        if self._rect_stage is not None:
+            self._rect_stage.after_post(self._maps['valid'])
+        for st in self._after:
+            st.run(self._maps, self._frames)
         return out
 
     def _capture(self):
-        cur = torch.cuda.current_stream()
-        side = torch.cuda.Stream()
-        side.wait_stream(cur)
-        with torch.no_grad(), _eval_mode(self.model):
-            with torch.cuda.stream(side):
-                self._run()  # warm-up (allocator, constants)
-            side.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=side):
-                out = self._run()
-        cur.wait_stream(side)
-        self._graph, self._out = g, out
+        self._graph, self._out = capture_graph(self.model, self._run)
 
     def refresh(self):
         """Re-fold and re-pack from the model's current weights and running
         statistics (in place: the captured graph stays valid unless a
         parameter's storage moved, which captures again)."""
-        before = self.infer._sites()
-        self.infer.refresh()
-        if self.capture and self.infer._sites() != before:
-            with torch.cuda.device(self._frames.device):
-                self._capture()
+        refresh_engine(self)
 
     def set_params(self, **kw):
         """any of focal_baseline, min_disparity, max_uncertainty, max_lr_error
         and, with ``render=``, render_lo, render_hi (a fixed range only),
         opacity, invalid_opacity and, with ``points=``, fx, fy, cx, cy: written
         into the device blocks in place, seen by the next call"""
-        known = PARAMS + (R.RENDER_PARAMS if self.render is not None else ()) + \
-            (P.INTR_PARAMS if self.points is not None else ())
+        known = PARAMS + sum((st.keys for st in self._after), ())
         bad = sorted(set(kw) - set(known))
         if bad:
             raise TypeError(f'DepthPipeline.set_params: unknown {bad}; one of {known}')
-        rkw = {k: kw.pop(k) for k in R.RENDER_PARAMS if k in kw}
-        if rkw:
-            fixed = [k for k in ('render_lo', 'render_hi') if k in rkw]
-            if fixed and self.render_auto:
-                raise ValueError(f"DepthPipeline.set_params: {fixed} on a pipeline built with "
-                                 f"render_range='auto' (the range is found per call)")
-            rkw = {k: R.check_number(f'DepthPipeline.set_params: {k}', v)
-                   for k, v in rkw.items()}
-        ikw = {k: kw.pop(k) for k in P.INTR_PARAMS if k in kw}
-        if ikw:
-            intr = P.check_intrinsics([ikw.get(k, self.intrinsics[k]) for k in P.INTR_PARAMS],
-                                      'DepthPipeline.set_params')
+        todo = []  # every stage checks its keys before anything is written
+        for st in self._after:
+            mine = {k: kw.pop(k) for k in st.keys if k in kw}
+            if mine:
+                todo.append((st, st.check_params(mine)))
         if kw:
-            self.params.update({k: float(v) for k, v in kw.items()})
-            self._params.copy_(torch.tensor([self.params[k] for k in PARAMS],
-                                            dtype=torch.float32))
-        if rkw:
-            self.render_params.update(rkw)
-            self._rparams.copy_(torch.tensor([self.render_params[k] for k in R.RENDER_PARAMS],
-                                             dtype=torch.float32))
-        if ikw:
-            self.intrinsics = dict(zip(P.INTR_PARAMS, intr))
-            self._intr.copy_(torch.tensor(intr, dtype=torch.float32))
+            _write(self._params, self.params, PARAMS, {k: float(v) for k, v in kw.items()})
+        for st, checked in todo:
+            _write(st.block, st.params, st.keys, checked)
 
     def set_calibration(self, how):
         """Another Calibration (or RemapTable) of the same mode and sizes:
         written into the device block (table) in place, seen by the next call
         without recapture.  Another mode or size is a ValueError."""
-        who = 'DepthPipeline.set_calibration'
-        if self.rectify is None:
-            raise ValueError(f'{who} on a pipeline built with rectify=None')
-        Q.check_how(how, who)
-        if how.mode != self.rectify.mode:
-            raise ValueError(f'{who}: a {type(how).__name__} on a pipeline built with a '
-                             f'{type(self.rectify).__name__}: build another pipeline')
-        size = tuple(how.out_size(self.src_shape[1:3]))
-        if size != tuple(self.frame_shape[1:3]):
-            raise ValueError(f'{who}: rectified size {size}, the pipeline was built for '
-                             f'{tuple(self.frame_shape[1:3])}: build another pipeline')
-        self._rect.copy_(how.data(None))
-        self.rectify = how
+        if self._rect_stage is None:
+            raise ValueError('DepthPipeline.set_calibration on a pipeline built with '
+                             'rectify=None')
+        self._rect_stage.set_calibration(how)
 
     def __call__(self, frames: torch.Tensor):
         _check_frames(frames, self.src_shape)
-        (self._frames if self.rectify is None else self._raw).copy_(frames, non_blocking=True)
+        self._input.copy_(frames, non_blocking=True)
         if self._graph is not None:
             self._graph.replay()
         else:
@@ -403,20 +283,11 @@ class DepthPipeline:
         """views of the static buffers of the last call (valid until the next one)"""
         if not self._called:
             raise L.UmamdError('DepthPipeline.last() before the first call')
-        out = {'disparity': self._disparity, 'depth': self._depth,
-               'uncertainty': self._uncertainty, 'lr_error': self._lr_error,
-               'valid': self._valid.view(torch.bool),
-               'prediction': self._out.permute(0, 3, 1, 2)[:, :4]}
-        if self.rectify is not None:
-            out['frame'] = self._frames
-            out['inside'] = self._inside.view(torch.bool)
-        if self.render is not None:
-            out['render'] = self._render
-        if self.points in ('map', 'both'):
-            out['xyz'] = self._xyz
-        if self.points in ('cloud', 'both'):
-            out.update(cloud_xyzu=self._cloud_xyzu, cloud_rgba=self._cloud_rgba,
-                       cloud_offsets=self._cloud_offsets)
+        out = {k: self._maps[k] for k in RENDERS}
+        out['valid'] = self._maps['valid'].view(torch.bool)
+        out['prediction'] = self._out.permute(0, 3, 1, 2)[:, :4]
+        for st in self._stages:
+            out.update(st.outputs())
         return out
 
     def cloud(self):
@@ -427,4 +298,5 @@ class DepthPipeline:
                                f"points={self.points!r}")
         if not self._called:
             raise L.UmamdError('DepthPipeline.cloud() before the first call')
-        return P.split(self._cloud_xyzu, self._cloud_rgba, self._cloud_offsets)
+        o = self._point_stage.outputs()
+        return split(o['cloud_xyzu'], o['cloud_rgba'], o['cloud_offsets'])

@@ -24,7 +24,7 @@ import torch
 
 from . import _lib as L
 from ._lib import call, ptr, query
-from .infer import InferenceEngine, _eval_mode
+from .infer import InferenceEngine, _eval_mode, capture_graph, check_prediction, refresh_engine
 
 KERNEL = 11   # the only pooling window um_eval_pool builds (the reference's)
 STEPS = 100   # sparsification steps (reference train/sparsification.py:9)
@@ -82,9 +82,7 @@ class EvaluationEngine:
     def _metrics(self, out):
         """every launch after the forward; ``out`` the prediction, NHWC f32"""
         B, _, H, W = self.shape
-        if out.dtype != torch.float32 or out.stride(3) != 1 or out.stride(1) != W * out.stride(2):
-            raise L.UmamdError(f'EvaluationEngine: prediction {out.dtype} with strides '
-                               f'{out.stride()} is not an NHWC f32 image')
+        check_prediction('EvaluationEngine', out, W)
         sn, sp = out.stride(0), out.stride(2)
         call('um_eval_maps', ptr(self._left), ptr(self._right), ptr(out), sn, sp, B, H, W,
              ptr(self._recon), ptr(self._err), ptr(self._maps_ws), ptr(self.acc))
@@ -106,31 +104,15 @@ class EvaluationEngine:
         return out
 
     def _capture(self):
-        cur = torch.cuda.current_stream()
-        side = torch.cuda.Stream()
-        side.wait_stream(cur)
-        with torch.no_grad(), _eval_mode(self.model):
-            with torch.cuda.stream(side):
-                self._run()  # warm-up (allocator, constants)
-            side.synchronize()
-            self.acc.zero_()  # the warm-up is not a batch
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=side):
-                out = self._run()
-        cur.wait_stream(side)
-        self._graph, self._out = g, out
+        acc = self.acc.clone()
+        self._graph, self._out = capture_graph(self.model, self._run)
+        self.acc.copy_(acc)  # the warm-up is not a batch
 
     def refresh(self):
         """Re-fold and re-pack from the model's current weights and running
         statistics (in place: the captured graph stays valid unless a
         parameter's storage moved, which captures again)."""
-        before = self.infer._sites()
-        self.infer.refresh()
-        if self.capture and self.infer._sites() != before:
-            acc = self.acc.clone()
-            with torch.cuda.device(self.acc.device):
-                self._capture()
-            self.acc.copy_(acc)
+        refresh_engine(self)
 
     def step(self, left: torch.Tensor, right: torch.Tensor, random_error=None) -> None:
         """one validation batch into the accumulators; no host sync"""

@@ -63,8 +63,44 @@ def _eval_mode(model):
             m.training = t
 
 
+def capture_graph(model, run):
+    """``run()`` once eagerly (the warm-up: allocator, constants), then once
+    under capture, on a side stream, in eval mode and without gradients ->
+    (the graph, what the captured run returned)"""
+    cur = torch.cuda.current_stream()
+    side = torch.cuda.Stream()
+    side.wait_stream(cur)
+    with torch.no_grad(), _eval_mode(model):
+        with torch.cuda.stream(side):
+            run()
+        side.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=side):
+            out = run()
+    cur.wait_stream(side)
+    return g, out
+
+
+def check_prediction(who: str, out: torch.Tensor, W: int):
+    """the metric and deployment kernels read the prediction as an NHWC f32
+    image of width ``W`` (any pixel and image stride)"""
+    if out.dtype != torch.float32 or out.stride(3) != 1 or out.stride(1) != W * out.stride(2):
+        raise UmamdError(f'{who}: prediction {out.dtype} with strides {out.stride()} is not an '
+                         f'NHWC f32 image')
+
+
+def refresh_engine(owner):
+    """``owner.infer`` re-folded and re-packed in place; ``owner._capture()``
+    again only if a parameter's storage moved (new sites) and it captures"""
+    before = owner.infer._sites()
+    owner.infer.refresh()
+    if owner.capture and owner.infer._sites() != before:
+        with torch.cuda.device(owner.infer._in.device):
+            owner._capture()
+
+
 class InferenceEngine:
-    """``eng = InferenceEngine(model, batch, height, width, scale=1.0)``;
+    """``eng =InferenceEngine(model, batch, height, width, scale=1.0)``;
     ``disparity, uncertainty = eng(left)`` with ``left`` [B,3,H,W] f32 on the
     device -> two [B,2,H,W] f32 tensors (the reference's
     ``torch.split(prediction, [2, 2], dim=1)``).
@@ -200,18 +236,7 @@ class InferenceEngine:
         return (len(self._pk.entries), len(self._fold), len(self._coef))
 
     def _capture(self):
-        cur = torch.cuda.current_stream()
-        side = torch.cuda.Stream()
-        side.wait_stream(cur)
-        with torch.no_grad(), _eval_mode(self.model):
-            with torch.cuda.stream(side):
-                self._forward()  # warm-up of the frozen path (allocator, constants)
-            side.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=side):
-                out = self._forward()
-        cur.wait_stream(side)
-        self._graph, self._out = g, out
+        self._graph, self._out = capture_graph(self.model, self._forward)
 
     def refresh(self):
         """Re-fold and re-pack from the model's current weights and running

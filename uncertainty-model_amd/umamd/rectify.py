@@ -16,7 +16,7 @@ integer coordinate, as in umamd.points.
   rectify(frames, how, out=None, inside=None)  -> (rectified, inside)
 
 ``umamd.deploy.DepthPipeline(rectify=...)`` runs the same entry as stage 0 of
-its captured graph.  Not built: R and P from stereo extrinsics (stereoRectify),
+its captured graph (``RectifyStage``).  Not built: R and P from stereo extrinsics (stereoRectify),
 fisheye and thin-prism models (use a RemapTable), bicubic sampling.
 """
 from __future__ import annotations
@@ -24,8 +24,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import _lib as L
-from ._lib import call, ptr
+from ._lib import call, check_same_device, check_tensor, ptr
 
 OUT = -2 ** 31  # the Q5 coordinate of a source position that is not finite or past 2^20
 MAX_SRC = 32767  # largest raw height / width (include/umamd.h)
@@ -205,6 +204,17 @@ def check_sizes(who: str, n: int, hs: int, ws: int, hr: int, wr: int):
         raise ValueError(f'{who}: {n} x {hr} x {wr} output pixels: from 1 to 2^31 - 1')
 
 
+def _remap(frames, mode, data, out, inside):
+    """um_frame_rectify on the current stream: ``frames`` [B, Hs, Ws, 3] ->
+    ``out`` [B, Hr, Wr, 3] and ``inside`` [Hr, Wr] through ``data``, the block
+    (``mode`` 'analytic') or the Q5 table ('table') on the device; no checks"""
+    b, hs, ws, _ = frames.shape
+    cal, table = (data, None) if mode == 'analytic' else (None, data)
+    call('um_frame_rectify', ptr(frames), b, hs, ws, out.shape[1], out.shape[2], ptr(cal),
+         ptr(table), ptr(out), ptr(inside))
+    return out, inside
+
+
 def rectify(frames: torch.Tensor, how, out=None, inside=None):
     """``frames`` uint8 [B, Hs, Ws, 3], contiguous, on the device -> ``(rectified
     uint8 [B, Hr, Wr, 3], inside uint8 [Hr, Wr])``: the frames sampled at the
@@ -215,9 +225,7 @@ def rectify(frames: torch.Tensor, how, out=None, inside=None):
     synchronises."""
     who = 'umamd.rectify.rectify'
     check_how(how, who)
-    if not torch.is_tensor(frames) or frames.dtype != torch.uint8:
-        raise TypeError(f'{who}: frames: uint8 tensor expected, got '
-                        f'{frames.dtype if torch.is_tensor(frames) else type(frames).__name__}')
+    check_tensor(who, 'frames', frames, (torch.uint8,), 'uint8')
     if frames.dim() != 4 or frames.shape[-1] != 3 or not frames.is_contiguous():
         raise ValueError(f'{who}: frames must be a contiguous [B, Hs, Ws, 3] batch (shape '
                          f'{tuple(frames.shape)}, strides {frames.stride()})')
@@ -225,26 +233,55 @@ def rectify(frames: torch.Tensor, how, out=None, inside=None):
     hr, wr = how.out_size((hs, ws))
     check_sizes(who, b, hs, ws, hr, wr)
     for name, t, shape in (('out', out, (b, hr, wr, 3)), ('inside', inside, (hr, wr))):
-        if t is None:
-            continue
-        if not torch.is_tensor(t) or t.dtype != torch.uint8:
-            raise TypeError(f'{who}: {name}: uint8 tensor expected, got '
-                            f'{t.dtype if torch.is_tensor(t) else type(t).__name__}')
-        if tuple(t.shape) != shape or not t.is_contiguous():
-            raise ValueError(f'{who}: {name}: contiguous {shape} expected, got {tuple(t.shape)} '
-                             f'with strides {t.stride()}')
-    L.require_device(frames)
+        if t is not None:
+            check_tensor(who, name, t, (torch.uint8,), 'uint8', shape)
+    check_same_device(who, 'frames', frames, out=out, inside=inside)
     dev = frames.device
-    for name, t in (('out', out), ('inside', inside)):
-        if t is not None and t.device != dev:
-            raise L.UmamdError(f'{who}: {name} on {t.device}, frames on {dev}')
     with torch.cuda.device(dev):
         if out is None:
             out = torch.empty((b, hr, wr, 3), dtype=torch.uint8, device=dev)
         if inside is None:
             inside = torch.empty((hr, wr), dtype=torch.uint8, device=dev)
-        data = how.data(dev)
-        cal, table = (data, None) if how.mode == 'analytic' else (None, data)
-        call('um_frame_rectify', ptr(frames), b, hs, ws, hr, wr, ptr(cal), ptr(table), ptr(out),
-             ptr(inside))
-    return out, inside
+        return _remap(frames, how.mode, how.data(dev), out, inside)
+
+
+class RectifyStage:
+    """Stage 0 of ``umamd.deploy.DepthPipeline``: ``how`` and the sizes, checked
+    on the host, its buffers, its two launches and its outputs."""
+
+    def __init__(self, how, batch, raw_height, raw_width):
+        self.how = check_how(how, 'DepthPipeline: rectify')
+        self.raw = (raw_height, raw_width)
+        self.size = tuple(how.out_size(self.raw))
+        if batch >= 1:  # the pipeline refuses another batch after its size checks
+            check_sizes('DepthPipeline: rectify', batch, *self.raw, *self.size)
+
+    def allocate(self, dev, B, Hs, Ws):
+        """(Hs, Ws): the rectified size, as for every later stage"""
+        self.raw_frames = torch.zeros((B,) + self.raw + (3,), dtype=torch.uint8, device=dev)
+        self.frames = torch.zeros((B, Hs, Ws, 3), dtype=torch.uint8, device=dev)
+        self._inside = torch.zeros((Hs, Ws), dtype=torch.uint8, device=dev)
+        self._data = self.how.data(dev)  # the f32[24] block or the Q5 table
+
+    def before_prep(self):
+        _remap(self.raw_frames, self.how.mode, self._data, self.frames, self._inside)
+
+    def after_post(self, valid):
+        """valid &= inside: the display and point stages see the combined mask"""
+        call('um_valid_and', ptr(valid), ptr(self._inside), valid.shape[0], self._inside.numel())
+
+    def outputs(self):
+        return {'frame': self.frames, 'inside': self._inside.view(torch.bool)}
+
+    def set_calibration(self, how):
+        who = 'DepthPipeline.set_calibration'
+        check_how(how, who)
+        if how.mode != self.how.mode:
+            raise ValueError(f'{who}: a {type(how).__name__} on a pipeline built with a '
+                             f'{type(self.how).__name__}: build another pipeline')
+        size = tuple(how.out_size(self.raw))
+        if size != self.size:
+            raise ValueError(f'{who}: rectified size {size}, the pipeline was built for '
+                             f'{self.size}: build another pipeline')
+        self._data.copy_(how.data(None))
+        self.how = how

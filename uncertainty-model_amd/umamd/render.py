@@ -13,14 +13,14 @@ for an f32 array.
   colourise(value)  uint8 value.shape + (3,), on the device
 
 ``umamd.deploy.DepthPipeline(render=...)`` runs the same two entries inside
-its captured graph.
+its captured graph: ``RenderStage`` is that stage.
 """
 from __future__ import annotations
 
 import torch
 
 from . import _lib as L
-from ._lib import call, ptr, query
+from ._lib import call, check_same_device, check_tensor, ptr, query
 
 # floor(plt.get_cmap('inferno')(arange(256))[:, :3] * 255 + 0.5), r g b per
 # entry: data, so that a deployment box needs no matplotlib for the default
@@ -44,6 +44,7 @@ _INFERNO = bytes.fromhex(
     'f2ea69f1ec6df1ed71f1ef75f1f179f2f27df2f482f3f586f3f68af4f88ef5f992f6fa96f8fb9af9fc9dfafda1fcffa4')
 
 RENDER_PARAMS = ('render_lo', 'render_hi', 'opacity', 'invalid_opacity')
+RENDERS = ('disparity', 'depth', 'uncertainty', 'lr_error')
 
 
 def lut(colour_map='inferno') -> torch.Tensor:
@@ -119,6 +120,15 @@ def value_range(value: torch.Tensor, valid=None, out=None, ws=None) -> torch.Ten
     return out
 
 
+def paint(value, valid, frame, table, block, auto, inverse, out) -> torch.Tensor:
+    """um_depth_render on the current stream into ``out``: ``block`` f32 [4]
+    (RENDER_PARAMS), ``auto`` None or the f32 [2] of ``value_range``, ``valid``
+    uint8 or None; no checks (the callers made them)."""
+    call('um_depth_render', ptr(value), ptr(valid), ptr(frame), value.numel(), ptr(table),
+         ptr(block), ptr(auto), int(bool(inverse)), ptr(out))
+    return out
+
+
 def colourise(value: torch.Tensor, lo=None, hi=None, valid=None, frame=None,
               colour_map='inferno', opacity: float = 1.0, invalid_opacity: float = 0.0,
               inverse: bool = False, out=None) -> torch.Tensor:
@@ -131,9 +141,7 @@ def colourise(value: torch.Tensor, lo=None, hi=None, valid=None, frame=None,
     found on the device.  NaN is black.  Runs on the current stream, never
     synchronises; ``out`` takes the result if given."""
     who = 'umamd.render.colourise'
-    if not torch.is_tensor(value) or value.dtype != torch.float32:
-        raise TypeError(f'{who}: value: f32 tensor expected, got '
-                        f'{value.dtype if torch.is_tensor(value) else type(value).__name__}')
+    check_tensor(who, 'value', value, (torch.float32,), 'f32')
     if not value.is_contiguous() or value.numel() == 0:
         raise ValueError(f'{who}: value must be contiguous and not empty (shape '
                          f'{tuple(value.shape)}, strides {value.stride()})')
@@ -143,34 +151,80 @@ def colourise(value: torch.Tensor, lo=None, hi=None, valid=None, frame=None,
     table = lut(colour_map)
     shape = tuple(value.shape)
     if valid is not None:
-        if not torch.is_tensor(valid) or valid.dtype not in (torch.bool, torch.uint8):
-            raise TypeError(f'{who}: valid: bool or uint8 tensor expected, got '
-                            f'{valid.dtype if torch.is_tensor(valid) else type(valid).__name__}')
-        if tuple(valid.shape) != shape or not valid.is_contiguous():
-            raise ValueError(f'{who}: valid: contiguous {shape} expected, got '
-                             f'{tuple(valid.shape)} with strides {valid.stride()}')
+        check_tensor(who, 'valid', valid, (torch.bool, torch.uint8), 'bool or uint8', shape)
     for name, t in (('frame', frame), ('out', out)):
-        if t is None:
-            continue
-        if not torch.is_tensor(t) or t.dtype != torch.uint8:
-            raise TypeError(f'{who}: {name}: uint8 tensor expected, got '
-                            f'{t.dtype if torch.is_tensor(t) else type(t).__name__}')
-        if tuple(t.shape) != shape + (3,) or not t.is_contiguous():
-            raise ValueError(f'{who}: {name}: contiguous {shape + (3,)} expected, got '
-                             f'{tuple(t.shape)} with strides {t.stride()}')
-    L.require_device(value)
-    for name, t in (('valid', valid), ('frame', frame), ('out', out)):
-        if t is not None and t.device != value.device:
-            raise L.UmamdError(f'{who}: {name} on {t.device}, value on {value.device}')
+        if t is not None:
+            check_tensor(who, name, t, (torch.uint8,), 'uint8', shape + (3,))
+    check_same_device(who, 'value', value, valid=valid, frame=frame, out=out)
     dev = value.device
     with torch.cuda.device(dev):
         if out is None:
             out = torch.empty(shape + (3,), dtype=torch.uint8, device=dev)
         if valid is not None and valid.dtype == torch.bool:
             valid = valid.view(torch.uint8)
-        table = table.to(dev)
-        rparams = torch.tensor([*(rng or (0.0, 1.0)), op, iop], dtype=torch.float32).to(dev)
+        block = torch.tensor([*(rng or (0.0, 1.0)), op, iop], dtype=torch.float32).to(dev)
         auto = value_range(value, valid) if rng is None else None
-        call('um_depth_render', ptr(value), ptr(valid), ptr(frame), value.numel(), ptr(table),
-             ptr(rparams), ptr(auto), int(bool(inverse)), ptr(out))
-    return out
+        return paint(value, valid, frame, table.to(dev), block, auto, inverse, out)
+
+
+class RenderStage:
+    """The display stage of ``umamd.deploy.DepthPipeline``: its arguments,
+    checked on the host, its buffers, its launches and its output."""
+
+    keys = RENDER_PARAMS  # of ``params`` and ``block``: what set_params takes
+
+    def __init__(self, render, colour_map, render_range, opacity, invalid_opacity, inverse):
+        if not isinstance(render, str) or render not in RENDERS:
+            raise ValueError(f'DepthPipeline: render={render!r}: None or one of {RENDERS}')
+        self.which = render
+        self.table = lut(colour_map)
+        bad = ValueError(f"DepthPipeline: render_range={render_range!r}: (lo, hi) or 'auto'")
+        if isinstance(render_range, str):
+            if render_range != 'auto':
+                raise bad
+            rng = None
+        else:
+            try:
+                lo, hi = render_range
+            except (TypeError, ValueError):
+                raise bad from None
+            rng = check_range(lo, hi, 'DepthPipeline: render_range')
+            if rng is None:
+                raise ValueError("DepthPipeline: render_range=(None, None): (lo, hi) or 'auto'")
+        self.auto = rng is None
+        lo, hi = rng or (0.0, 1.0)  # 'auto': replaced by the device range
+        self.params = {'render_lo': lo, 'render_hi': hi,
+                       'opacity': check_number('DepthPipeline: opacity', opacity),
+                       'invalid_opacity': check_number('DepthPipeline: invalid_opacity',
+                                                       invalid_opacity)}
+        self.inverse = bool(inverse)
+
+    def allocate(self, dev, B, Hs, Ws):
+        self.block = torch.tensor(list(self.params.values()), dtype=torch.float32, device=dev)
+        self._lut = self.table.to(dev)
+        self._out = torch.zeros((B, Hs, Ws, 3), dtype=torch.uint8, device=dev)
+        self._range = self._range_ws = None
+        if self.auto:
+            self._range = torch.zeros(2, dtype=torch.float32, device=dev)
+            self._range_ws = torch.zeros(query('um_value_range_ws', B * Hs * Ws),
+                                         dtype=torch.uint8, device=dev)
+
+    def run(self, maps, frames):
+        """``maps``: the pipeline's disparity, depth, uncertainty, lr_error and
+        valid (uint8) buffers; ``frames`` the frame they were computed from"""
+        value = maps[self.which]
+        if self.auto:
+            value_range(value, maps['valid'], out=self._range, ws=self._range_ws)
+        paint(value, maps['valid'], frames, self._lut, self.block, self._range, self.inverse,
+              self._out)
+
+    def outputs(self):
+        return {'render': self._out}
+
+    def check_params(self, kw):
+        """the stage's part of set_params, checked (nothing is written yet)"""
+        fixed = [k for k in ('render_lo', 'render_hi') if k in kw]
+        if fixed and self.auto:
+            raise ValueError(f"DepthPipeline.set_params: {fixed} on a pipeline built with "
+                             f"render_range='auto' (the range is found per call)")
+        return {k: check_number(f'DepthPipeline.set_params: {k}', v) for k, v in kw.items()}
