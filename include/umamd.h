@@ -953,6 +953,85 @@ int um_frame_rectify(const unsigned char* src, int N, int Hs, int Ws, int Hr, in
                      unsigned char* inside, hipStream_t stream);
 int um_valid_and(unsigned char* valid, const unsigned char* inside, int N, long HW,
                  hipStream_t stream);
+/* Refinement (umamd/refine.py, DepthPipeline(refine=...)): a stage of our own
+ * between um_depth_post and um_valid_and; the reference has none.  In both
+ * kernels every float step below is one exactly rounded f32 operation, in the
+ * order written, IEEE division, no contraction.  fp: DEVICE f32[8] = (eps, a,
+ * floor, q, g2, 0, 0, 0); the kernels read it and the tables, so a captured
+ * graph sees new values at its next replay.  "finite": neither NaN nor +-inf.
+ *
+ * um_disp_smooth: a dilated joint-bilateral filter weighted by confidence.
+ * disp, unc f32 [N][Hs][Ws]; frame u8 [N][Hs][Ws][3], the guide; radius R and
+ * dilation step: the taps sit at offsets (j*step, i*step) (rows, columns), j
+ * and i in [-R, R]; S f32 [(R+1)*(R+1)] indexed [|j|][|i|], the spatial table;
+ * G f32 [768], the colour table.  -> disp_out, unc_out f32 [N][Hs][Ws],
+ * distinct from the inputs.  For output pixel p the taps t are visited in
+ * row-major order (j outer, i inner, both ascending).  A tap takes part only
+ * if it lies inside the image and disp[t] and unc[t] are both finite; every
+ * other tap is skipped (no border is replicated, a skipped tap is not read):
+ *   c_t = 1 / (unc[t]*unc[t] + eps)
+ *   k   = |r_p - r_t| + |g_p - g_t| + |b_p - b_t|        (integer, 0..765)
+ *   w   = (S[|j|][|i|] * G[k]) * c_t
+ *   num = num + w*disp[t];   nus = nus + w*unc[t];   den = den + w
+ * (num, nus, den start at 0).  If den > 0 and den is finite, disp_out[p] =
+ * num/den and unc_out[p] = nus/den; otherwise disp[p] and unc[p] pass through
+ * bit for bit.  The host makes S = exp(-(i*i + j*j) / (2 sigma_s^2)) (sigma_s
+ * in taps) and G = exp(-k*k / (2 sigma_c^2)) (sigma_c in summed 8-bit levels)
+ * in f64 and rounds them to f32; any other table is as valid.
+ * One launch.  A workgroup of 256 threads owns a tile of 64 columns x 16 rows
+ * (8 rows where R*step > 13) and stages the tile and its halo of R*step
+ * pixels in LDS once, as four planes: disp, unc, c (computed once per staged
+ * pixel) and the packed colour with the takes-part flag in byte 3; G lives in
+ * LDS too.  A wave owns one tile row at a time, so its 64 lanes read 64
+ * consecutive dwords of a plane for every tap, whatever the step: no bank
+ * conflict but in the G lookup, whose index is data.  k is one v_sad_u8.  No
+ * atomics, no state between calls.
+ * Limits: 1 <= R <= 3, step >= 1, R*step <= 16, N, Hs, Ws >= 1, N*Hs*Ws <=
+ * INT_MAX.  UM_ERR_ARG before any launch: a value outside them, a null
+ * pointer, a float pointer that is not 4-byte aligned.
+ *
+ * um_disp_fuse: a per-pixel recursive filter over the frames of a stream plus
+ * finalise.  disp_in, unc_in, lr_error f32 [count]; params: the DEVICE f32[4]
+ * block of um_depth_post (fb, min_disp, max_unc, max_lr); state mean, var f32
+ * [count], both given or both NULL, var < 0 marking an empty state (reset: a
+ * fill of var with -1).  With state, for pixel i, d = disp_in[i], s =
+ * unc_in[i]:
+ *   t = a*s;  m = t*t + floor;  fresh = finite(d) && finite(m)
+ *   p = var[i] + q;  e = d - mean[i];  pm = p + m
+ *   keep = fresh && var[i] >= 0 && e*e <= g2*pm
+ *   keep:          K = p/pm;  mean' = mean[i] + K*e;  var' = p - K*p
+ *   !keep, fresh:  mean' = d;  var' = m                      (reset)
+ *   !fresh:        mean' = mean[i];  var' = var[i]           (state untouched)
+ *   D = var' >= 0 ? mean' : d;   U = s;   disp_var[i] = var'
+ * and mean', var' are stored.  Without state D = d, U = s and disp_var is not
+ * written.  Then, as um_depth_post: depth = D > min_disp ? fb / D : 0; valid =
+ * D > min_disp && U <= max_unc && lr_error[i] <= max_lr (0 / 1).  Outputs
+ * disparity (D), uncertainty (U), depth, valid (u8), disp_var: any may be
+ * NULL.  The model's sigma is a photometric quantity: a (noise_scale) turns it
+ * into a disparity noise and floor keeps the gain below 1.
+ * One launch, one thread per 4 pixels with 16-byte accesses, a scalar form
+ * for the tail and for bases that are not aligned (floats 16, valid 4).
+ * Elementwise: an output may be its own input (disp_in == disparity).
+ * UM_ERR_ARG before any launch: count < 1; a null disp_in / unc_in / params /
+ * fp; valid without lr_error; one of mean and var alone; a float pointer that
+ * is not 4-byte aligned.
+ *
+ * Measured inside DepthPipeline's graph (tools/bench_depth_refine.py, MI355X,
+ * 1024x1280 -> 256x512 bf16, B=1, R=2, step=2, medians of 3 alternated
+ * repeats, uniform-noise frames): 'spatial' (um_disp_smooth + um_disp_fuse
+ * without state) adds 0.0392 ms to the 1.1909 ms frame, 'temporal' (um_disp_fuse)
+ * 0.0099 ms, 'both' 0.0435 ms; the maps of 'both' composed from torch device
+ * ops (25 shifted-slice taps, elementwise filter) after the plain pipeline add
+ * 2.5978 ms (59.7x).  'both' beat the composition in each of the 3 repeats; the
+ * composition's five maps differ from the stage's in 0 of 1 310 720 elements
+ * each. */
+int um_disp_smooth(const float* disp, const float* unc, const unsigned char* frame, int N, int Hs,
+                   int Ws, int R, int step, const float* S, const float* G, const float* fp,
+                   float* disp_out, float* unc_out, hipStream_t stream);
+int um_disp_fuse(const float* disp_in, const float* unc_in, const float* lr_error, long count,
+                 const float* params, const float* fp, float* mean, float* var, float* disparity,
+                 float* uncertainty, float* depth, unsigned char* valid, float* disp_var,
+                 hipStream_t stream);
 
 /* ------------------------------------------------ SyncBN exchange (IPC) ---
  * SyncBatchNorm statistics exchanged device-side over IPC-mapped per-rank

@@ -201,6 +201,8 @@ _SIG = {
     'um_depth_cloud': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, 's']),
     'um_frame_rectify': (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, 's']),
     'um_valid_and': (_I, [_P, _P, _I, _L, 's']),
+    'um_disp_smooth': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, 's']),
+    'um_disp_fuse': (_I, [_P, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, 's']),
     'um_adam_chunk': (_I, []),
     'um_adam_step_dev': (_I, [_P, _P, _I, _F, _P, _F, _F, _F, _F, _P, 's']),
 }
@@ -355,6 +357,13 @@ def check_same_device(who: str, name: str, first: torch.Tensor, **others):
     for k, t in others.items():
         if t is not None and t.device != first.device:
             raise UmamdError(f'{who}: {k} on {t.device}, {name} on {first.device}')
+
+
+def write_block(block: torch.Tensor, params: dict, keys, new: dict):
+    """``new`` into the host dict ``params`` and the whole device ``block``
+    (its values in the order of ``keys``), in place"""
+    params.update(new)
+    block.copy_(torch.tensor([params[k] for k in keys], dtype=torch.float32))
 
 
 def dtype_code(dt: torch.dtype) -> int:

@@ -22,6 +22,16 @@ adds both ends of the deployment path,
                   (umamd/points.py; after um_depth_post, independent of the
                   display stage)
 
+With ``refine=`` a stage sits straight after um_depth_post, in the same graph
+(umamd/refine.py), and the display and point stages read what it wrote:
+
+  um_disp_smooth  only 'spatial' and 'both': disparity and uncertainty
+                  filtered along the edges of the full-resolution frame, each
+                  tap weighted by its confidence
+  um_disp_fuse    'temporal' and 'both': the disparity fused per pixel with
+                  the stream's state; always: depth and the mask of the
+                  refined maps (um_depth_post leaves these two to it)
+
 captured as ONE torch.cuda.CUDAGraph over static buffers.  ``__call__``
 copies the frames in and replays; it never synchronises with the host.  The
 calibration and the three thresholds live in a 4-float device block the kernel
@@ -47,20 +57,15 @@ import math
 import torch
 
 from . import _lib as L
-from ._lib import call, ptr, query
+from ._lib import call, ptr, query, write_block
 from .imageprep import resize_coeffs
 from .infer import InferenceEngine, _eval_mode, capture_graph, check_prediction, refresh_engine
 from .points import POINTS, PointStage, split  # noqa: F401 (POINTS: a name of this module too)
 from .rectify import RectifyStage
+from .refine import NOISE_SCALE, PROCESS_NOISE, REFINES, VAR_FLOOR, RefineStage  # noqa: F401
 from .render import RENDERS, RenderStage
 
 PARAMS = ('focal_baseline', 'min_disparity', 'max_uncertainty', 'max_lr_error')
-
-
-def _write(block, params, keys, new):
-    """``new`` into the host dict and the whole device block (in place)"""
-    params.update(new)
-    block.copy_(torch.tensor([params[k] for k in keys], dtype=torch.float32))
 
 
 def _check_frames(frames, shape):
@@ -136,7 +141,30 @@ class DepthPipeline:
     ``.intrinsics``.  ``set_calibration(how)`` replaces the block or the table
     in place (same mode and sizes), seen by the next call without recapture.
     With ``rectify=None`` (the default) nothing of this is allocated, launched
-    or returned."""
+    or returned.
+
+    ``refine='spatial' | 'temporal' | 'both'`` adds the refine stage to the
+    same graph (umamd/refine.py; include/umamd.h has the definition).
+    ``disparity``, ``uncertainty``, ``depth`` and ``valid`` are then the
+    REFINED maps -- the display and point stages read them -- ``lr_error``
+    stays raw, and ``out['raw_disparity']`` and ``out['raw_uncertainty']`` hold
+    what um_depth_post produced.  ``'spatial'``: a joint-bilateral filter of
+    ``(2 * refine_radius + 1)^2`` taps ``refine_step`` pixels apart (None:
+    ``max(1, round(Ws / width))``, one model pixel), weighted by distance
+    (``sigma_space``, taps), by the colour difference to the centre in the
+    frame (``sigma_colour``, summed 8-bit levels) and by the tap's confidence
+    ``1 / (uncertainty^2 + conf_eps)``.  ``'temporal'``: a per-pixel recursive
+    filter over the calls, the measurement noise ``(noise_scale *
+    uncertainty)^2 + var_floor``, the state's variance growing by
+    ``process_noise`` per call, a measurement further than ``gate`` standard
+    deviations from the state restarting it; ``out['disparity_var']`` is the
+    state's variance (source pixels squared).  There is no motion
+    compensation: the filter suits a camera that moves little between frames.
+    ``'both'``: the first, then the second.  The state is empty after
+    construction, ``refresh()`` and ``reset_refine()``.  ``set_params`` then
+    also takes the seven float parameters (tables and block rewritten in
+    place); radius and step are fixed.  With ``refine=None`` (the default)
+    nothing of this is allocated, launched or returned."""
 
     def __init__(self, model, src_height: int, src_width: int, batch: int = 1, height: int = 256,
                  width: int = 512, scale: float = 1.0, focal_baseline: float = 1.0,
@@ -144,7 +172,11 @@ class DepthPipeline:
                  max_lr_error: float = math.inf, fused: bool = True, capture: bool = True,
                  render=None, colour_map='inferno', render_range='auto', opacity: float = 1.0,
                  invalid_opacity: float = 0.0, inverse: bool = False, points=None,
-                 intrinsics=None, point_stride: int = 1, rectify=None):
+                 intrinsics=None, point_stride: int = 1, rectify=None, refine=None,
+                 refine_radius: int = 2, refine_step=None, sigma_space: float = 1.5,
+                 sigma_colour: float = 30.0, conf_eps: float = 1e-4,
+                 noise_scale: float = NOISE_SCALE, var_floor: float = VAR_FLOOR,
+                 process_noise: float = PROCESS_NOISE, gate: float = 3.0):
         # every stage checks its own arguments, in this order, before any GPU work
         self._render_stage = None if render is None else RenderStage(
             render, colour_map, render_range, opacity, invalid_opacity, inverse)
@@ -156,6 +188,12 @@ class DepthPipeline:
         self.src_shape = (B, Hs, Ws, 3)  # the camera's raw size
         if rect is not None:
             Hs, Ws = rect.size  # the rectified size from here on
+        if refine_step is None and W > 0:
+            refine_step = max(1, round(Ws / W))  # one model pixel
+        self._refine_stage = None if refine is None else RefineStage(
+            refine, refine_radius, refine_step, sigma_space, sigma_colour, conf_eps, noise_scale,
+            var_floor, process_noise, gate)
+        self.refine = refine
         if H <= 0 or W <= 0 or H % 32 or W % 32:
             raise ValueError(f'image size {H}x{W}: height and width must be multiples of 32')
         if Hs < 2 or Ws < 2:
@@ -179,7 +217,8 @@ class DepthPipeline:
         self.capture = bool(capture)
         dev = self.infer._in.device
         self._after = [st for st in (self._render_stage, self._point_stage) if st is not None]
-        self._stages = ([] if rect is None else [rect]) + self._after
+        self._tunable = [st for st in [self._refine_stage] + self._after if st is not None]
+        self._stages = [st for st in (rect, self._refine_stage) if st is not None] + self._after
         for st in self._stages:
             st.allocate(dev, B, Hs, Ws)
         self._frames = torch.zeros(self.frame_shape, dtype=torch.uint8, device=dev) \
@@ -209,10 +248,14 @@ class DepthPipeline:
     inverse = property(lambda self: self._render_stage.inverse)
     intrinsics = property(lambda self: self._point_stage.params)
     point_stride = property(lambda self: self._point_stage.stride)
+    refine_params = property(lambda self: self._refine_stage.params)
+    refine_radius = property(lambda self: self._refine_stage.radius)
+    refine_step = property(lambda self: self._refine_stage.step)
 
     # ---------------------------------------------------------------- runs --
     def _run(self):
-        """rectify -> prep -> forward -> post -> mask-and -> render -> points"""
+        """rectify -> prep -> forward -> post -> refine -> mask-and -> render ->
+        points"""
         B, _, H, W = self.shape
         _, Hs, Ws, _ = self.frame_shape
         bh, kh, bv, kv = self._tables
@@ -222,8 +265,13 @@ class DepthPipeline:
              ptr(bv), ptr(kv), self._ks[1], ptr(self.infer._in))
         out = self.infer._forward()
         check_prediction('DepthPipeline', out, W)
+        post = self._maps
+        if self._refine_stage is not None:
+            post = {**post, **self._refine_stage.post_targets()}
         call('um_depth_post', ptr(out), out.stride(0), out.stride(2), B, H, W, Hs, Ws,
-             ptr(self._params), *[ptr(self._maps[k]) for k in RENDERS + ('valid',)])
+             ptr(self._params), *[ptr(post[k]) for k in RENDERS + ('valid',)])
+        if self._refine_stage is not None:
+            self._refine_stage.run(self._maps, self._frames, self._params)
         if self._rect_stage is not None:
             self._rect_stage.after_post(self._maps['valid'])
         for st in self._after:
@@ -232,31 +280,41 @@ class DepthPipeline:
 
     def _capture(self):
         self._graph, self._out = capture_graph(self.model, self._run)
+        self.reset_refine()  # the warm-up run before the capture fused a frame
+
+    def reset_refine(self):
+        """Empty the temporal state of the refine stage: the next call starts
+        a new stream.  Nothing to do without the stage or with 'spatial'."""
+        if self._refine_stage is not None:
+            self._refine_stage.reset()
 
     def refresh(self):
         """Re-fold and re-pack from the model's current weights and running
         statistics (in place: the captured graph stays valid unless a
         parameter's storage moved, which captures again)."""
         refresh_engine(self)
+        self.reset_refine()  # other weights: the stream starts again
 
     def set_params(self, **kw):
         """any of focal_baseline, min_disparity, max_uncertainty, max_lr_error
         and, with ``render=``, render_lo, render_hi (a fixed range only),
-        opacity, invalid_opacity and, with ``points=``, fx, fy, cx, cy: written
-        into the device blocks in place, seen by the next call"""
-        known = PARAMS + sum((st.keys for st in self._after), ())
+        opacity, invalid_opacity and, with ``points=``, fx, fy, cx, cy and, with
+        ``refine=``, sigma_space, sigma_colour, conf_eps, noise_scale, var_floor,
+        process_noise, gate: written into the device blocks (and tables) in
+        place, seen by the next call"""
+        known = PARAMS + sum((st.keys for st in self._tunable), ())
         bad = sorted(set(kw) - set(known))
         if bad:
             raise TypeError(f'DepthPipeline.set_params: unknown {bad}; one of {known}')
         todo = []  # every stage checks its keys before anything is written
-        for st in self._after:
+        for st in self._tunable:
             mine = {k: kw.pop(k) for k in st.keys if k in kw}
             if mine:
                 todo.append((st, st.check_params(mine)))
         if kw:
-            _write(self._params, self.params, PARAMS, {k: float(v) for k, v in kw.items()})
+            write_block(self._params, self.params, PARAMS, {k: float(v) for k, v in kw.items()})
         for st, checked in todo:
-            _write(st.block, st.params, st.keys, checked)
+            st.write(checked)
 
     def set_calibration(self, how):
         """Another Calibration (or RemapTable) of the same mode and sizes:

@@ -23,7 +23,7 @@ import math
 
 import torch
 
-from ._lib import call, check_same_device, check_tensor, ptr, query
+from ._lib import call, check_same_device, check_tensor, ptr, query, write_block
 
 INTR_PARAMS = ('fx', 'fy', 'cx', 'cy')
 POINTS = ('map', 'cloud', 'both')
@@ -208,3 +208,7 @@ class PointStage:
         """the stage's part of set_params, checked (nothing is written yet)"""
         new = [kw.get(k, self.params[k]) for k in INTR_PARAMS]
         return dict(zip(INTR_PARAMS, check_intrinsics(new, 'DepthPipeline.set_params')))
+
+    def write(self, checked):
+        """``checked`` into the host dict and the device block, in place"""
+        write_block(self.block, self.params, self.keys, checked)

@@ -20,7 +20,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib as L
-from ._lib import call, check_same_device, check_tensor, ptr, query
+from ._lib import call, check_same_device, check_tensor, ptr, query, write_block
 
 # floor(plt.get_cmap('inferno')(arange(256))[:, :3] * 255 + 0.5), r g b per
 # entry: data, so that a deployment box needs no matplotlib for the default
@@ -228,3 +228,7 @@ class RenderStage:
             raise ValueError(f"DepthPipeline.set_params: {fixed} on a pipeline built with "
                              f"render_range='auto' (the range is found per call)")
         return {k: check_number(f'DepthPipeline.set_params: {k}', v) for k, v in kw.items()}
+
+    def write(self, checked):
+        """``checked`` into the host dict and the device block, in place"""
+        write_block(self.block, self.params, self.keys, checked)
